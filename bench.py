@@ -4,8 +4,11 @@
 
 A step = one y = A*x over the workload's matrix, through the C-ABI plan (the automatically chosen
 kernel: the panel sweep for the power-law matrix, the flagged tiles for the banded one), with A,
-x and y resident in HBM before the timed region. The K timed steps are replayed from one hipGraph
-(spmv_plan_run_graph, captured and warmed before the timed region); the same K steps with one
+x and y resident in HBM before the timed region. The K timed steps (--steps K) are replayed from
+one hipGraph (spmv_plan_run_graph, captured and warmed before the timed region); ms_per_step is
+that replay's time / K. A plain run does this and no more: set-up, W warm-up steps, the K timed
+steps, the y of the last one written out if --dump-outputs DIR is given, and the result line.
+Everything else below is measured and checked only with --full: then the same K steps with one
 host launch each are timed first (graph.eager_ms_per_step), and their HIP-event kernel times give
 the roofline. For a split plan (the N >= 4 strong-scaling slices: panels cut into pieces whose
 partial sums a second kernel adds) the graph carries the combine of step k as extra blocks of step
@@ -24,14 +27,14 @@ Multi-GPU (--gpus N, one process per GPU, torch.distributed over RCCL):
       max-over-ranks time of one SpMV (compute-only: every rank's slice, no collective inside
       the timed step). The y exchange (RCCL gather of the disjoint slices, RCCL reduce of
       full-length partials = accum_results' +=, and the all-gather of the iterative form) is
-      timed separately in "exchange", with the end-to-end rate beside it.
+      timed separately in "exchange" (--full), with the end-to-end rate beside it.
   --scaling weak: rank r owns its own 10M-row / 160M-nnz row partition of an (N*10M) x 10M
-      matrix; value = total nnz of all ranks * 2 / max-over-ranks time. A strong run reports the
+      matrix; value = total nnz of all ranks * 2 / max-over-ranks time. A strong --full run reports the
       weak measurement as the side field "weak_companion" (and a weak run the strong one as
       "strong_companion").
 
-Extra JSON fields: roofline (dominant kernel of the plan: k_spmv_sweep_packed for the power-law
-matrix, k_spmv_tiles for the banded one; HIP events on its launch stream),
+Extra JSON fields of a --full run (null in a plain one):
+roofline (dominant kernel of the plan: k_spmv_sweep_packed for the power-law matrix, k_spmv_tiles for the banded one; HIP events on its launch stream),
 cpu_baseline (the oracle's restatement of spmv_gold, 1 thread, on the host of the GPU box),
 parity (full-size componentwise-scaled error vs that oracle run; mandatory at every N: a failed
 or missing check prints value null / valid false and exits 3), dropin (the drop-in boundary
@@ -81,8 +84,17 @@ def parse(argv=None):
     ap.add_argument("--nnz", type=int, default=None)
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None,
                     help="default: strong (config 4) when --gpus > 1, weak (= single GPU) otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the eager pass and its roofline, the full-size parity check "
+                         "against the oracle, the CPU baseline, the drop-in run, the side kernels and "
+                         "configurations, the host copies and, at N > 1, the exchange forms and companions. "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the y of the last timed step as DIR/y.npy (rank r of "
+                         "N > 1: its slice, DIR/y_rank<r>.npy); a y above the size limit is written as a "
+                         "fixed, seeded sample of its rows, whose indices go to DIR/y_rows.npy")
     ap.add_argument("--no-cpu", action="store_true",
-                    help="skip the CPU baseline timing (the full-size parity check always runs)")
+                    help="--full: skip the CPU baseline timing (the full-size parity check always runs)")
     ap.add_argument("--no-dropin", action="store_true",
                     help="skip the drop-in boundary measurement (create_csr_hw_matrix -> spmv_hw -> "
                          "verification in a child process, the reference's run.elf timings)")
@@ -459,6 +471,26 @@ def host_csr(rp, col, val, x, y):
     timed region."""
     return {"rp": rp.cpu().numpy().view(np.uint32), "col": col.cpu().numpy().view(np.uint32),
             "val": val.cpu().numpy(), "x": x.cpu().numpy(), "y": y.cpu().numpy()}
+
+
+DUMP_BUDGET_BYTES = 48_000_000  # --dump-outputs: all files of a run together stay below 64 MB
+
+
+def dump_outputs(path, y, rank, world):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- this rank's
+    y -- as float32 / float64 .npy. A y that does not fit this rank's share of the budget is cut
+    to a sample of its rows, drawn once from a fixed seed (the same rows for the same size, so
+    two builds are compared row for row); their indices are written beside it, as float64."""
+    os.makedirs(path, exist_ok=True)
+    h = y.detach().cpu().numpy()
+    sfx = "" if world == 1 else f"_rank{rank}"
+    budget = DUMP_BUDGET_BYTES // world
+    if h.nbytes > budget:
+        k = budget // (h.itemsize + 8)
+        rows = np.sort(np.random.default_rng(160_000_000).choice(h.shape[0], size=k, replace=False))
+        np.save(os.path.join(path, f"y_rows{sfx}.npy"), rows.astype(np.float64))
+        h = h[rows]
+    np.save(os.path.join(path, f"y{sfx}.npy"), np.ascontiguousarray(h))
 
 
 def _oracle():
@@ -1209,8 +1241,9 @@ def main():
     y = torch.empty(st["nr_rows"], dtype=x.dtype, device=dev)
     torch.cuda.synchronize()
     setup_s = time.perf_counter() - t_setup
-    keep_csr = not args.multi  # N = 1: the full-size parity check reads the matrix after the timed region
-    want_xtiles = not args.multi and args.workload == "powerlaw" and not args.no_xtiles
+    # --full, N = 1: the full-size parity check reads the matrix after the timed region
+    keep_csr = args.full and not args.multi
+    want_xtiles = args.full and not args.multi and args.workload == "powerlaw" and not args.no_xtiles
     if not keep_csr and not want_xtiles:
         del rp, col, val
         torch.cuda.empty_cache()
@@ -1223,24 +1256,26 @@ def main():
     stage("timed")
     if os.environ.get("SPMV_BENCH_INJECT") == "hang" and rank == world - 1:
         time.sleep(3600)  # test hook (tests/test_gpu_bench.py): a rank that never reaches the barrier
-    # 1) eager: one host launch per step, the main kernel timed with HIP events on its stream
-    #    (roofline.achieved; rocprofv3 sees the same launches)
+    # 1) --full, eager: one host launch per step, the main kernel timed with HIP events on its
+    #    stream (roofline.achieved; rocprofv3 sees the same launches)
     barrier(world)
     torch.cuda.synchronize()
-    plan.set_timing(True)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        plan.run(x, y, stream)
-    torch.cuda.synchronize()
-    barrier(world)
-    t1 = time.perf_counter()
-    kernel_ms, _, launches = plan.timing()
-    plan.set_timing(False)
-    eager_ms = spmv_dist.max_over_ranks((t1 - t0) * 1e3 / args.steps, dev)
-    kernel_ms_max = spmv_dist.max_over_ranks(kernel_ms, dev)
-    per_rank = [0.0] * world  # every rank's dominant-kernel time (load balance of the slices)
-    per_rank[rank] = kernel_ms
-    kernel_ms_ranks = spmv_dist.sum_over_ranks(per_rank, dev) if args.multi else [kernel_ms]
+    eager_ms = kernel_ms_max = None
+    if args.full:
+        plan.set_timing(True)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            plan.run(x, y, stream)
+        torch.cuda.synchronize()
+        barrier(world)
+        t1 = time.perf_counter()
+        kernel_ms, _, launches = plan.timing()
+        plan.set_timing(False)
+        eager_ms = spmv_dist.max_over_ranks((t1 - t0) * 1e3 / args.steps, dev)
+        kernel_ms_max = spmv_dist.max_over_ranks(kernel_ms, dev)
+        per_rank = [0.0] * world  # every rank's dominant-kernel time (load balance of the slices)
+        per_rank[rank] = kernel_ms
+        kernel_ms_ranks = spmv_dist.sum_over_ranks(per_rank, dev) if args.multi else [kernel_ms]
 
     # 2) the headline: the same K steps replayed from one hipGraph (spmv_plan_run_graph, captured
     #    and warmed once, untimed) -- no host launch gap between steps
@@ -1264,7 +1299,7 @@ def main():
     else:
         ms = serial_chain_ms(plan, x, y, args.steps, world, dev)
     graph = {"iters": args.steps, "ms_per_step": round(ms, 5), "timed": "headline (value, ms_per_step)",
-             "eager_ms_per_step": round(eager_ms, 5),
+             "eager_ms_per_step": round(eager_ms, 5) if args.full else None,
              "value_form": "serial: each SpMV (sweep, then the combine of a split plan) ends before the next begins",
              # how spmv_plan_run_graph orders the steps (plan stats format bits 8 / 9)
              "run_graph_form": product_form, "run_graph_ms_per_step": round(product_ms, 5)}
@@ -1276,6 +1311,9 @@ def main():
                           "spmv_plan_run_graph on a split plan (step k's combine inside step k + 1's sweep: "
                           "independent SpMVs only); dependent = x <- A x with the all-gather exchange in every "
                           "step (compute + exchange)"}
+
+    if args.dump_outputs:  # y of the last timed step, before anything else writes to it
+        dump_outputs(args.dump_outputs, y, rank, world)
 
     xtiles = det = binned = None
     if want_xtiles:  # reported beside the headline, never fatal to it
@@ -1299,8 +1337,8 @@ def main():
 
     # the Part-1 boundary (spmv_hw) hands over host buffers: PCIe cost of x in and y out,
     # pinned host memory (reported only; never part of `value`)
-    host = {}
-    for name, t in (("x_h2d_ms", x), ("y_d2h_ms", y)):
+    host = {} if args.full else None
+    for name, t in (("x_h2d_ms", x), ("y_d2h_ms", y)) if args.full else ():
         h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
         reps = 3
         torch.cuda.synchronize()
@@ -1321,11 +1359,12 @@ def main():
         alg_all -= (world - 1) * (st["nr_cols"] * np.dtype(dtype).itemsize + 4)
 
     gflops = 2.0 * nnz_all / (ms * 1e-3) / 1e9
-    graph["eager_gflops"] = round(2.0 * nnz_all / (eager_ms * 1e-3) / 1e9, 3)
+    graph["eager_gflops"] = round(2.0 * nnz_all / (eager_ms * 1e-3) / 1e9, 3) if args.full else None
     eff_gbps = alg_all / (ms * 1e-3) / 1e9
     # roofline of the dominant kernel: algorithmic bytes of one launch / mean launch duration
     # (max over ranks: every rank's dominant kernel has the same per-launch algorithmic bytes)
-    kernel_ms = kernel_ms_max
+    # (--full only: the kernel's time comes from the eager pass)
+    kernel_ms = kernel_ms_max if args.full else 0.0
     achieved = alg_local / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
     # the dominant kernel of this plan; its PMC traffic is taken from profiles/traffic.json only
     # when that summary was recorded for the same workload, size and kernel
@@ -1345,7 +1384,7 @@ def main():
         kname = "k_spmv_tiles"
     traffic = None
     l2_requests = None  # TCC_HIT_sum + TCC_MISS_sum per launch, same PMC passes
-    if os.path.exists(args.traffic):
+    if args.full and os.path.exists(args.traffic):
         try:
             tr = json.load(open(args.traffic))
             key = f"{desc['workload']}_{args.dtype}"
@@ -1396,6 +1435,7 @@ def main():
         "slice_of": args.slice_of,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(ms, 5),
         "higher_is_better": True,
         "scaling": args.scaling if args.multi else "weak",
@@ -1405,7 +1445,8 @@ def main():
         "config": dict(desc, parallelism=f"row-slice x{world}", dtype=args.dtype),
         "effective_GBps": round(eff_gbps, 2),
         "roofline_pct": round(100.0 * eff_gbps / (HBM_PEAK_GBPS * world), 2),
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
+        "roofline": None if not args.full else
+                    {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
                      "peak_measured": stream_peak,
                      "frac_of_measured": round(achieved / stream_peak, 4) if stream_peak else None,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
@@ -1446,6 +1487,26 @@ def main():
         emit()
         print(f"bench.py rank {rank}: {what}: {detail}", file=sys.stderr, flush=True)
         os._exit(3)
+
+    def finish():
+        """The line (with value_e2e: the end-to-end rate beside the compute-only value, VERDICT r5
+        item 4 -- one SpMV plus the exchange that completes y, as the reference's "Total time" is
+        hardware + accumulation, csr_hw_wrapper.cpp:276-285), then the teardown."""
+        out["value_e2e"], out["value_e2e_form"] = value_e2e(out, ms, nnz_all)
+        emit()
+        # the line is out: a teardown that hangs (plan or process-group destruction) must not hold
+        # the run (under torch.distributed.run no parent would end it before --run-timeout)
+        teardown = threading.Timer(args.spawn_grace, lambda: os._exit(0))
+        teardown.daemon = True
+        teardown.start()
+        plan.destroy()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        if run_watchdog is not None:
+            run_watchdog.cancel()
+
+    if not args.full:  # the headline alone: what follows checks and measures beside it
+        return finish()
 
     # parity is part of the measurement, not an extra (main.cpp:77-82 verifies every spmv_hw
     # result), at every N. It runs under the run deadline and the collective timeout only, before
@@ -1638,22 +1699,8 @@ def main():
     ref = None
     if not args.multi and args.workload == "powerlaw" and args.dtype == "f64" and not args.no_side_configs:
         guarded("side_configs", lambda: {name: side_config(args, name, dev, stream) for name in ("config2", "config5")})
-    # the end-to-end rate beside the compute-only value: one SpMV plus the
-    # exchange that completes y, as the reference's "Total time" is hardware + accumulation
-    # (csr_hw_wrapper.cpp:276-285)
-    out["value_e2e"], out["value_e2e_form"] = value_e2e(out, ms, nnz_all)
     watchdog.cancel()
-    emit()
-    # the line is out and verified: a teardown that hangs (plan or process-group destruction) must
-    # not hold the run (under torch.distributed.run no parent would end it before --run-timeout)
-    teardown = threading.Timer(args.spawn_grace, lambda: os._exit(0))
-    teardown.daemon = True
-    teardown.start()
-    plan.destroy()
-    if dist.is_initialized():
-        dist.destroy_process_group()
-    if run_watchdog is not None:
-        run_watchdog.cancel()
+    finish()
 
 
 if __name__ == "__main__":

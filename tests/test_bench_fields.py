@@ -60,6 +60,45 @@ def test_reference_line_parser():
     assert bench._ref_lines(text, "Software execution time") == []
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a y within the budget is written whole in its own precision; a larger one
+    as the same seeded sample of rows on every call, with the rows beside it; N ranks share the
+    budget and write one file each."""
+    import numpy as np
+    import torch
+
+    assert bench.DUMP_BUDGET_BYTES + 16 * 1024 <= 64_000_000  # 64 MB in all, 16 .npy headers included
+    y = torch.arange(1000, dtype=torch.float32) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), y, 0, 1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["y.npy"]
+    got = np.load(tmp_path / "a" / "y.npy", allow_pickle=False)
+    assert got.dtype == np.float32 and np.array_equal(got, y.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2400)
+    y64 = y.double()
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), y64, 0, 1)
+    rows = np.load(tmp_path / "b" / "y_rows.npy", allow_pickle=False)
+    vals = np.load(tmp_path / "b" / "y.npy", allow_pickle=False)
+    assert rows.dtype == np.float64 and vals.dtype == np.float64 and len(rows) == len(vals) == 150
+    assert rows.nbytes + vals.nbytes <= 2400
+    r = rows.astype(np.int64)
+    assert np.all(np.diff(r) > 0) and r[0] >= 0 and r[-1] < 1000 and np.array_equal(vals, y64.numpy()[r])
+    for f in ("y.npy", "y_rows.npy"):
+        assert (tmp_path / "b" / f).read_bytes() == (tmp_path / "c" / f).read_bytes()
+
+    bench.dump_outputs(str(tmp_path / "d"), y64, 1, 2)  # rank 1 of 2: half the budget
+    assert sorted(os.listdir(tmp_path / "d")) == ["y_rank1.npy", "y_rows_rank1.npy"]
+    assert len(np.load(tmp_path / "d" / "y_rank1.npy", allow_pickle=False)) == 75
+
+
+def test_plain_and_full_options_parse():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
 def test_dropin_child_is_in_the_package():
     """The drop-in run is the package's own script (no oracle import: it takes the software y
     from the bench)."""

@@ -17,15 +17,19 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--rows", "400000", "--nnz", "6400000", "--steps", "3", "--warmup", "1", "--extras-timeout", "150"]
+# --full: the checks and side measurements these tests read are behind it
+SMALL = ["--full", "--rows", "400000", "--nnz", "6400000", "--steps", "3", "--warmup", "1", "--extras-timeout", "150"]
 
 
-def _bench(*args, env=None, want_rc=0):
+PLAIN = ["--gpus", "1", "--rows", "400000", "--nnz", "6400000", "--steps", "3", "--warmup", "1"]
+
+
+def _bench(*args, env=None, want_rc=0, base=SMALL):
     e = {k: v for k, v in os.environ.items()
          if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     e.update(env or {})
     # its own process group: on a timeout the self-launched ranks go with the parent
-    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, *args], stdout=subprocess.PIPE,
+    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), *base, *args], stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, env=e, cwd=ROOT, start_new_session=True)
     try:
         out, err = p.communicate(timeout=280)
@@ -63,6 +67,43 @@ def test_bench_one_gpu_line():
     assert abs(di["total_ms"] - di["hardware_execution_ms"] - di["result_accumulation_ms"]) < 1e-3
     assert di["software_execution_ms"] > 0 and di["storage_mb"] > 0
     assert len(di["unstreamed_total_ms"]["calls"]) == 5 and di["unstreamed_total_ms"]["median"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_y(tmp_path):
+    """Without --full the run times its steps and prints the line: the headline fields are there,
+    everything that takes a run or a check of its own is null. --dump-outputs writes the y of the
+    last timed step; the inputs are the generator's (fixed seeds), so the y is held here to the
+    oracle's spmv_gold of the same matrix regenerated in this process, at the bound the --full
+    line's own parity meets at this size (scaled error 1e-12, fp64)."""
+    import numpy as np
+    import torch
+
+    import oracle
+    import spmv_hw
+
+    out = tmp_path / "dump"
+    d = _bench("--dump-outputs", str(out), base=PLAIN)
+    assert d["metric"] == "SpMV GFLOP/s + effective HBM GB/s (% roofline), fp64, 1/2/4/8 MI355X"
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["unit"] == "GFLOP/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["ms_per_step"] > 0 and d["graph"]["iters"] == 3 and d["graph"]["ms_per_step"] == d["ms_per_step"]
+    assert d["value"] == pytest.approx(2 * 6_400_000 / (d["ms_per_step"] * 1e-3) / 1e9, rel=1e-3)
+    assert d["value_e2e"] == d["value"]
+    for k in ("parity", "roofline", "cpu_baseline", "side_configs", "lds_xtiles", "binned", "deterministic",
+              "host_copy", "exchange"):
+        assert d[k] is None, k
+    assert "dropin" not in d and d["graph"]["eager_ms_per_step"] is None
+    assert sorted(os.listdir(out)) == ["y.npy"]
+    y = np.load(out / "y.npy", allow_pickle=False)
+    assert y.dtype == np.float64 and y.shape == (400_000,)
+    lib = spmv_hw.load(np.float64)
+    rp, col, val, _ = spmv_hw.gen_powerlaw(lib, 400_000, 400_000, 6_400_000, seed=4)
+    x = spmv_hw.gen_vector(lib, 400_000, seed=6)
+    torch.cuda.synchronize()
+    h_rp, h_col = rp.cpu().numpy().view(np.uint32), col.cpu().numpy().view(np.uint32)
+    h_val, h_x = val.cpu().numpy(), x.cpu().numpy()
+    ref = oracle.spmv_gold(h_rp, h_col, h_val, h_x)
+    assert oracle.scaled_error(h_rp, h_col, h_val, h_x, ref, y) <= 1e-12
 
 
 @pytest.mark.parametrize("scaling", ["strong", "weak"])
