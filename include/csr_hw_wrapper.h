@@ -163,6 +163,41 @@ int spmv_plan_set_timing(spmv_plan *plan, int enable);
 int spmv_plan_get_timing(spmv_plan *plan, double *mean_ms, double *total_ms, int *launches);
 void spmv_plan_destroy(spmv_plan *plan);
 
+/* Several right-hand sides at once: Y = A * X for nvec (1..8) vectors. d_X is nr_cols x nvec and
+ * d_Y nr_rows x nvec, both row-major (X[c * nvec + j] is column c of vector j): a contiguous
+ * tensor of shape (n, nvec). Both pointers must be aligned to min(16, nvec * sizeof(ValueType))
+ * bytes (for nvec 3, 5, 6, 7, whose rows are no power of two: to the largest power of two that
+ * divides a row, at most 16). Column j of Y is what spmv_plan_run gives for column j of X.
+ *   native = 1: one pass over the slice layout (kernel 5) for nvec 2, 4 or 8, the matrix read
+ *     once for all vectors. Taken with env SPMV_HW_KERNEL=slices, or automatically (no
+ *     SPMV_HW_KERNEL) when the slice layout's padding, 64 * slots / nnz, stays under the measured
+ *     limit. fp64, and fp32 with env SPMV_SLICE_ACC=32, are bitwise spmv_gold.
+ *   native = 0: the handle owns an ordinary plan (built as spmv_plan_create_device builds it, so
+ *     any other SPMV_HW_KERNEL value holds) and scratch of nvec * (nr_cols + nr_rows) values; a
+ *     run splits X into nvec contiguous vectors, runs the plan nvec times and interleaves the
+ *     results into Y. nvec = 1 runs the plan on X and Y directly.
+ * spmv_multi_run overwrites Y (empty rows get 0), is asynchronous on `stream` and enqueues only
+ * kernels and memsets (capturable); all scratch is allocated at create, and runs of one handle
+ * must be ordered, as for spmv_plan_run. A bad nvec, a null handle or a misaligned pointer
+ * returns nonzero before anything is enqueued. */
+typedef struct spmv_multi spmv_multi;
+typedef struct spmv_multi_stats {
+    uint64_t nr_rows, nr_cols, nr_nzeros;
+    uint64_t device_bytes;       /* representation + scratch resident in HBM */
+    uint64_t algorithmic_bytes;  /* CSR bytes + nvec * (x + y) bytes per run */
+    int32_t  device, nvec;
+    int32_t  native;             /* 1: one-pass multi-vector kernel; 0: per-vector fallback */
+    int32_t  kernel, format;     /* of the underlying plan, as spmv_plan_stats */
+} spmv_multi_stats;
+int spmv_multi_create_device(spmv_multi **m, int device, uint32_t nr_rows, uint32_t nr_cols,
+                             uint32_t nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col_ind,
+                             const ValueType *d_values, int nvec, void *stream);
+int spmv_multi_create_host(spmv_multi **m, int device, const csr_matrix *matrix,
+                           uint32_t row_begin, uint32_t row_end, int nvec);
+int spmv_multi_run(const spmv_multi *m, const ValueType *d_X, ValueType *d_Y, void *stream);
+int spmv_multi_get_stats(const spmv_multi *m, spmv_multi_stats *stats);
+void spmv_multi_destroy(spmv_multi *m);
+
 /* nnz-balanced contiguous row partition into `units` slices: bounds[0]=0, bounds[units]=nr_rows,
  * slice u = rows [bounds[u], bounds[u+1]) with ~nnz/units non-zeros each (the
  * reference's S1 rule, csr_hw.cpp:459, without the FPGA alignment rules S2/S3). Host only. */

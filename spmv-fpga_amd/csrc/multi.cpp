@@ -1,0 +1,264 @@
+// spmv_multi: Y = A * X for 1..8 right-hand sides per call (include/csr_hw_wrapper.h Part 2).
+//
+// Native path: the slice plan's one-pass kernel for 2, 4 or 8 vectors (slices.hip,
+// k_spmv_slices_multi). Fallback, for every other kernel and vector count: an ordinary plan,
+// X split into contiguous vectors, one plan run per vector, the results interleaved into Y.
+// The reference multiplies by one vector per call (spmv.cpp:280-294 copies one x per CU).
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+
+#include "spmv_internal.hpp"
+
+using namespace spmvhw;
+
+struct spmv_multi {
+    spmv_plan *plan = nullptr;
+    int nvec = 1;
+    bool native = false;
+    ValueType *d_xs = nullptr;  // fallback: nvec contiguous vectors of nr_cols
+    ValueType *d_ys = nullptr;  // fallback: nvec contiguous results of nr_rows
+    ~spmv_multi()
+    {
+        if (plan) {
+            (void)hipSetDevice(plan->device);
+            (void)hipDeviceSynchronize();
+        }
+        if (d_xs)
+            (void)hipFree(d_xs);
+        if (d_ys)
+            (void)hipFree(d_ys);
+        delete plan;
+    }
+};
+
+namespace spmvhw {
+
+// The automatic choice's padding limit: the native path is taken while 64 * slots <= limit * nnz.
+// Each limit is the highest padding at which the native path beat the fallback by more than the
+// two measurements' spread on the power-law generator (500k rows, 16 per row, rows capped so
+// that the padding is 1.25 .. 6; tools/multi_bench.py --crossover, profiles/multi_bench.jsonl
+// tag "crossover"). fp64, fallback on the sweep: nvec 2 wins at 1.5 (0.087 vs
+// 0.093 ms) and ties at 1.75; nvec 4 wins at 4.0 (0.170 vs 0.178) and loses at 5.0; nvec 8 wins
+// at 6.0 (0.279 vs 0.350). fp32, fallback on the tiles: nvec 2 wins at 3.0 (0.080 vs 0.095) and
+// is within 2 % at 4.0; nvec 4 (0.160 vs 0.184) and nvec 8 (0.217 vs 0.361) win at 6.0, the last padding
+// measured with capped rows.
+static double multi_pad_limit(int nvec)
+{
+    if (sizeof(ValueType) == 8)
+        return nvec == 2 ? 1.5 : nvec == 4 ? 4.0 : 6.0;
+    return nvec == 2 ? 3.0 : 6.0;
+}
+
+// dst[j * n + i] = src[i * K + j]: X (row-major, K per row) into K contiguous vectors. A wave
+// reads 64 consecutive values and writes K runs of 64 / K.
+__global__ void k_multi_split(const ValueType *__restrict__ src, ValueType *__restrict__ dst, uint64_t n, uint32_t K)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n * K)
+        dst[(t % K) * n + t / K] = src[t];
+}
+
+// dst[i * K + j] = src[j * n + i]: K contiguous results into Y (row-major)
+__global__ void k_multi_join(const ValueType *__restrict__ src, ValueType *__restrict__ dst, uint64_t n, uint32_t K)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n * K)
+        dst[t] = src[(t % K) * n + t / K];
+}
+
+static bool multi_native_nvec(int nvec) { return nvec == 2 || nvec == 4 || nvec == 8; }
+
+// 64-row slices' stored entries (64 * slots) from row_ptr alone, as build_slices counts them
+static uint64_t slice_stored_entries(const IndexType *rp, IndexType n)
+{
+    uint64_t slots = 0;
+    for (uint64_t q = 0; q < n; q += kWave) {
+        uint32_t L = 0;
+        for (uint64_t r = q; r < std::min<uint64_t>(n, q + kWave); ++r)
+            L = std::max<uint32_t>(L, rp[r + 1] - rp[r]);
+        slots += L;
+    }
+    return slots * kWave;
+}
+
+// rp: rebased host row_ptr. Decides the path, builds the plan and the fallback's scratch.
+static int multi_create(spmv_multi **out, int device, IndexType nr_rows, IndexType nr_cols, const IndexType *rp,
+                        const IndexType *col, const ValueType *val, bool on_device, int nvec, hipStream_t s)
+{
+    const char *env = std::getenv("SPMV_HW_KERNEL");
+    const bool automatic = !env || !*env || !std::strcmp(env, "auto");
+    bool native = false;
+    if (multi_native_nvec(nvec)) {
+        if (env && !std::strcmp(env, "slices")) {
+            native = true;
+        } else if (automatic && nr_rows) {
+            const uint64_t nnz = rp[nr_rows], stored = slice_stored_entries(rp, nr_rows);
+            native = nnz > 0 && stored <= 0xFFFFFFFFull && double(stored) <= multi_pad_limit(nvec) * double(nnz);
+        }
+    }
+    std::unique_ptr<spmv_multi> m(new spmv_multi());
+    m->nvec = nvec;
+    m->native = native;
+    if (plan_create_from_host_rowptr(&m->plan, device, nr_rows, nr_cols, rp, col, val, on_device, s,
+                                     native ? kKernelSlices : -1))
+        return 1;
+    if (native && m->plan->kernel != kKernelSlices) {
+        set_error("spmv_multi: internal: the native path needs a slice plan");
+        return 1;
+    }
+    if (native) {
+        (void)launch_slices_multi(*m->plan, nvec, nullptr, nullptr, s, true);  // load the code object
+        (void)hipGetLastError();
+    } else if (nvec > 1) {
+        SPMV_TRY(hipMalloc((void **)&m->d_xs, std::max<uint64_t>(uint64_t(nr_cols) * nvec, 1) * sizeof(ValueType)));
+        SPMV_TRY(hipMalloc((void **)&m->d_ys, std::max<uint64_t>(uint64_t(nr_rows) * nvec, 1) * sizeof(ValueType)));
+        launch_or_warm(true, k_multi_split, dim3(1), dim3(256), 0, s, (const ValueType *)nullptr, (ValueType *)nullptr,
+                       uint64_t(0), 0u);
+        launch_or_warm(true, k_multi_join, dim3(1), dim3(256), 0, s, (const ValueType *)nullptr, (ValueType *)nullptr,
+                       uint64_t(0), 0u);
+        (void)hipGetLastError();
+    }
+    *out = m.release();
+    return 0;
+}
+
+static bool multi_bad_nvec(const char *who, int nvec)
+{
+    if (nvec >= 1 && nvec <= 8)
+        return false;
+    set_error(std::string(who) + ": nvec must be 1..8");
+    return true;
+}
+
+}  // namespace spmvhw
+
+extern "C" {
+
+int spmv_multi_create_device(spmv_multi **m, int device, IndexType nr_rows, IndexType nr_cols, IndexType nr_nzeros,
+                             const IndexType *d_row_ptr, const IndexType *d_col_ind, const ValueType *d_values,
+                             int nvec, void *stream)
+{
+    if (!m || (nr_rows && !d_row_ptr)) {
+        set_error("spmv_multi_create_device: null argument");
+        return 1;
+    }
+    *m = nullptr;
+    if (multi_bad_nvec("spmv_multi_create_device", nvec))
+        return 1;
+    hipStream_t s = (hipStream_t)stream;
+    SPMV_TRY(hipSetDevice(device));
+    std::vector<IndexType> rp(size_t(nr_rows) + 1, 0u);
+    if (nr_rows) {
+        SPMV_TRY(hipMemcpyAsync(rp.data(), d_row_ptr, rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
+        SPMV_TRY(hipStreamSynchronize(s));
+    }
+    const IndexType base = rp[0];
+    for (auto &e : rp)
+        e -= base;
+    if (rp[nr_rows] != nr_nzeros) {
+        set_error("spmv_multi_create_device: row_ptr[n]-row_ptr[0] != nr_nzeros");
+        return 1;
+    }
+    return multi_create(m, device, nr_rows, nr_cols, rp.data(), d_col_ind ? d_col_ind + base : nullptr,
+                        d_values ? d_values + base : nullptr, true, nvec, s);
+}
+
+int spmv_multi_create_host(spmv_multi **m, int device, const csr_matrix *mat, IndexType row_begin, IndexType row_end,
+                           int nvec)
+{
+    if (!m || !mat || row_begin > row_end || row_end > mat->nr_rows) {
+        set_error("spmv_multi_create_host: bad arguments");
+        return 1;
+    }
+    *m = nullptr;
+    if (multi_bad_nvec("spmv_multi_create_host", nvec))
+        return 1;
+    const IndexType n = row_end - row_begin;
+    const IndexType base = mat->row_ptr[row_begin];
+    std::vector<IndexType> rp(size_t(n) + 1);
+    for (IndexType r = 0; r <= n; ++r)
+        rp[r] = mat->row_ptr[row_begin + r] - base;
+    return multi_create(m, device, n, mat->nr_cols, rp.data(), mat->col_ind + base, mat->values + base, false, nvec,
+                        nullptr);
+}
+
+int spmv_multi_run(const spmv_multi *m, const ValueType *d_X, ValueType *d_Y, void *stream)
+{
+    // a pointer that is not even aligned to one value is misaligned for every nvec: refused
+    // before the handle is looked at
+    if (uintptr_t(d_X) % sizeof(ValueType) || uintptr_t(d_Y) % sizeof(ValueType)) {
+        set_error("spmv_multi_run: misaligned X or Y (not a multiple of sizeof(ValueType))");
+        return 1;
+    }
+    if (!m) {
+        set_error("spmv_multi_run: null handle");
+        return 1;
+    }
+    // a row of X or Y is nvec values: min(16, nvec * sizeof(ValueType)) bytes for nvec 1, 2, 4, 8;
+    // for the other counts (fallback only) the largest power of two that divides a row, up to 16
+    const uintptr_t rowb = uintptr_t(m->nvec) * sizeof(ValueType);
+    const uintptr_t align = std::min<uintptr_t>(16, rowb & (~rowb + 1));
+    if (uintptr_t(d_X) % align || uintptr_t(d_Y) % align) {
+        set_error("spmv_multi_run: misaligned X or Y (need " + std::to_string(align) + " bytes for this nvec)");
+        return 1;
+    }
+    const spmv_plan &p = *m->plan;
+    hipStream_t s = (hipStream_t)stream;
+    if (p.nr_rows == 0)
+        return 0;
+    if (!d_X || !d_Y) {
+        set_error("spmv_multi_run: null X or Y");
+        return 1;
+    }
+    SPMV_TRY(hipSetDevice(p.device));
+    if (m->native) {
+        SPMV_TRY(launch_slices_multi(p, m->nvec, d_X, d_Y, s));
+        return 0;
+    }
+    if (m->nvec == 1)
+        return spmv_plan_run(&p, d_X, d_Y, stream);
+    const uint32_t K = (uint32_t)m->nvec;
+    const uint64_t nx = uint64_t(p.nr_cols) * K, ny = uint64_t(p.nr_rows) * K;
+    if (nx) {
+        hipLaunchKernelGGL(k_multi_split, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, d_X, m->d_xs,
+                           uint64_t(p.nr_cols), K);
+        SPMV_TRY(hipGetLastError());
+    }
+    for (uint32_t j = 0; j < K; ++j)
+        if (spmv_plan_run(&p, m->d_xs + uint64_t(j) * p.nr_cols, m->d_ys + uint64_t(j) * p.nr_rows, stream))
+            return 1;
+    hipLaunchKernelGGL(k_multi_join, dim3((unsigned)((ny + 255) / 256)), dim3(256), 0, s, (const ValueType *)m->d_ys,
+                       d_Y, uint64_t(p.nr_rows), K);
+    SPMV_TRY(hipGetLastError());
+    return 0;
+}
+
+int spmv_multi_get_stats(const spmv_multi *m, spmv_multi_stats *st)
+{
+    if (!m || !st) {
+        set_error("spmv_multi_get_stats: null argument");
+        return 1;
+    }
+    spmv_plan_stats ps;
+    if (spmv_plan_get_stats(m->plan, &ps))
+        return 1;
+    std::memset(st, 0, sizeof(*st));
+    const uint64_t vecs = uint64_t(m->nvec) * (ps.nr_cols + ps.nr_rows) * sizeof(ValueType);
+    st->nr_rows = ps.nr_rows;
+    st->nr_cols = ps.nr_cols;
+    st->nr_nzeros = ps.nr_nzeros;
+    st->device_bytes = ps.device_bytes + (m->d_xs ? vecs : 0);
+    st->algorithmic_bytes = ps.nr_nzeros * (sizeof(ValueType) + 4) + (ps.nr_rows + 1) * 4 + vecs;
+    st->device = ps.device;
+    st->nvec = m->nvec;
+    st->native = m->native ? 1 : 0;
+    st->kernel = ps.kernel;
+    st->format = ps.format;
+    return 0;
+}
+
+void spmv_multi_destroy(spmv_multi *m) { delete m; }
+
+}  // extern "C"

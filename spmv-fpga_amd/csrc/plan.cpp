@@ -479,7 +479,7 @@ static int time_layout(spmv_plan &P, const ValueType *d_x, ValueType *d_y, hipSt
 
 int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows, IndexType nr_cols,
                                  const IndexType *h_row_ptr, const IndexType *col_src,
-                                 const ValueType *val_src, bool src_on_device, hipStream_t s)
+                                 const ValueType *val_src, bool src_on_device, hipStream_t s, int force_kernel)
 {
     *out = nullptr;
     PhaseTrace trace;
@@ -540,7 +540,8 @@ int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows,
         }
     }
 
-    int kernel = requested_kernel();
+    const int requested = force_kernel >= 0 ? force_kernel : requested_kernel();
+    int kernel = requested;
     const bool tune = kernel == kKernelTune;
     if (kernel == -1 || tune) {  // (tune: the automatic choice is the preferred candidate)
         // automatic choice: the sweep pays once x outgrows ~half an XCD's L2 and the columns of a
@@ -651,7 +652,7 @@ int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows,
         for (int c = 0; c < 4; ++c)
             p->tuned_ms[c] = tuned[c];
         trace("tune: build + time each", s);
-    } else if (requested_kernel() < 0 && kernel == kKernelTiles && nnz >= 65536) {
+    } else if (requested < 0 && kernel == kKernelTiles && nnz >= 65536) {
         // automatic, local columns: the slice layout when rows of a 64-row slice have about the
         // same length (<= 15 % padding) and every slot fits 16-bit (or clustered 16-bit) offsets
         // -- finite-element / stencil-like matrices, where it is 7-14 % faster than the tiles
@@ -678,7 +679,7 @@ int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows,
             trace("build tile layout", s);
         }
     } else {
-        if (kernel == kKernelBinned && requested_kernel() < 0) {
+        if (kernel == kKernelBinned && requested < 0) {
             p->bin_skew_limit = 2.0;  // automatic: skewed matrices stay on the sweep
             // and so do matrices with a row above 0.3x a panel's mean entries: 2M x 6M fp32 with
             // 64 rows of L (profiles/r03e_skew_rowlimit.jsonl; L / mean 0.12, 0.24, 0.44, 0.81):
@@ -687,7 +688,7 @@ int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows,
             if (const char *e = std::getenv("SPMV_BIN_ROW_LIMIT"))
                 p->bin_row_limit = std::atof(e);
         }
-        if (build_layout(*p, kernel, requested_kernel() < 0, h_row_ptr, d_col, d_val, s))
+        if (build_layout(*p, kernel, requested < 0, h_row_ptr, d_col, d_val, s))
             return 1;
         trace(p->kernel == kKernelSweep ? "build sweep layout" : p->kernel == kKernelBinned ? "build binned layout"
               : p->kernel != kKernelTiles ? "build CSR layout"

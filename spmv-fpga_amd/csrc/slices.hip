@@ -169,6 +169,208 @@ __global__ __launch_bounds__(kSliceThreads) void k_spmv_slices(const V *__restri
         y[row] = V(acc);
 }
 
+// ---- K right-hand sides in one pass (spmv_multi, multi.cpp) ----
+//
+// The same walk over the same representation with X and Y row-major (X[col * K + j]): a lane
+// gathers its entry's K consecutive x values as 16-byte (8-byte: fp32 K = 2) chunks and keeps K
+// row sums, so the matrix stream is read once for K vectors and the wave stores 64 * K
+// consecutive values of Y. Column j of Y sees exactly k_spmv_slices' operations on column j of X
+// (separate multiply and add, the select between them, CSR order from +0).
+template <typename V, int K>
+struct MultiChunk {
+    static constexpr int kBytes = K * sizeof(V) >= 16 ? 16 : 8;
+    static constexpr int kElems = kBytes / sizeof(V);  // values per chunk
+    static constexpr int kChunks = K / kElems;         // chunks per entry
+    typedef V T __attribute__((ext_vector_type(kElems)));
+};
+
+// pairs of slots in flight per iteration. The single-vector kernel's 8 gathers of one value
+// become 8 / K gathers of K values, which was the starting point; K = 8 measured 1-14 % faster
+// with 2 pairs than with 1, and every other neighbouring setting slower on at least one matrix
+// (DESIGN.md §14 has the measurement and the register table). The macros are the tuning handle.
+#ifndef SPMV_MULTI_PAIRS_K2
+#define SPMV_MULTI_PAIRS_K2 4
+#endif
+#ifndef SPMV_MULTI_PAIRS_K4
+#define SPMV_MULTI_PAIRS_K4 2
+#endif
+#ifndef SPMV_MULTI_PAIRS_K8
+#define SPMV_MULTI_PAIRS_K8 2
+#endif
+constexpr int multi_pairs(int K) { return K == 2 ? SPMV_MULTI_PAIRS_K2 : K == 4 ? SPMV_MULTI_PAIRS_K4 : SPMV_MULTI_PAIRS_K8; }
+
+template <typename V, int OB, int K, int PU, typename A>
+__global__ __launch_bounds__(kSliceThreads) void k_spmv_slices_multi(
+    const V *__restrict__ val, const void *__restrict__ offv, const uint32_t *__restrict__ sbase,
+    const uint32_t *__restrict__ slot_off, const uint32_t *__restrict__ len, const V *__restrict__ X, V *__restrict__ Y,
+    uint32_t nrows, uint32_t nslices)
+{
+#pragma clang fp contract(off)
+    typedef typename SliceVec<V>::T VT;
+    typedef typename SliceOff<OB>::S OS;
+    typedef typename SliceOff<OB>::T OT;
+    typedef MultiChunk<V, K> MC;
+    typedef typename MC::T XT;
+    constexpr int NC = MC::kChunks, CE = MC::kElems;
+    constexpr uint32_t m = OB == 3 ? 0x3FFFu : 0xFFFFFFFFu;
+    const OS *__restrict__ off = reinterpret_cast<const OS *>(offv);
+    const uint32_t s = blockIdx.x * (kSliceThreads / kWave) + (threadIdx.x >> 6);
+    if (s >= nslices)
+        return;  // wave-uniform
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t row = s * kWave + lane;
+    const uint32_t j0 = __builtin_amdgcn_readfirstlane(slot_off[s]);
+    const uint32_t L = __builtin_amdgcn_readfirstlane(slot_off[s + 1]) - j0;
+    const uint32_t mylen = row < nrows ? len[row] : 0u;
+    const uint32_t npairs = L / 2;
+    A acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        acc[k] = A(0);
+    for (uint32_t p = 0; p < npairs; p += PU) {
+        VT v[PU];
+        OT o[PU];
+        uint32_t b0[PU], b1[PU];
+#pragma unroll
+        for (int u = 0; u < PU; ++u) {
+            if (p + u >= npairs) {  // wave-uniform: a pair past the slice's end is skipped
+                v[u] = VT(0);
+                o[u] = OT(0);
+                b0[u] = b1[u] = 0u;
+                continue;
+            }
+            const uint32_t pp = p + u;
+            const uint64_t e = (uint64_t)(j0 + 2 * pp) * kWave + 2 * lane;
+            v[u] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(val + e));
+            o[u] = __builtin_nontemporal_load(reinterpret_cast<const OT *>(off + e));
+            if constexpr (OB == 3) {  // per-lane pick among the slot's 4 bases (scalar loads)
+                const uint32_t *b = sbase + 4 * (j0 + 2 * pp);
+                const uint32_t k0 = o[u].x >> 14, k1 = o[u].y >> 14;
+                b0[u] = k0 == 0 ? b[0] : k0 == 1 ? b[1] : k0 == 2 ? b[2] : b[3];
+                b1[u] = k1 == 0 ? b[4] : k1 == 1 ? b[5] : k1 == 2 ? b[6] : b[7];
+            } else {
+                b0[u] = sbase[j0 + 2 * pp];
+                b1[u] = sbase[j0 + 2 * pp + 1];
+            }
+        }
+        XT x0[PU][NC], x1[PU][NC];
+#pragma unroll
+        for (int u = 0; u < PU; ++u) {
+            if (p + u >= npairs) {  // wave-uniform: no gather for a skipped pair
+#pragma unroll
+                for (int c = 0; c < NC; ++c)
+                    x0[u][c] = x1[u][c] = XT(0);
+                continue;
+            }
+            // 64-bit: col * K passes 2^32 from 2^29 columns at K = 8
+            const XT *g0 = reinterpret_cast<const XT *>(X + (uint64_t)(b0[u] + (o[u].x & m)) * K);
+            const XT *g1 = reinterpret_cast<const XT *>(X + (uint64_t)(b1[u] + (o[u].y & m)) * K);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                x0[u][c] = g0[c];
+                x1[u][c] = g1[c];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PU; ++u) {
+            const uint32_t j = 2 * (p + u);  // slot of the pair's first entry
+            const bool in0 = p + u < npairs && j < mylen, in1 = p + u < npairs && j + 1 < mylen;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const A t0 = A(v[u].x) * A(x0[u][k / CE][k % CE]);
+                const A t1 = A(v[u].y) * A(x1[u][k / CE][k % CE]);
+                acc[k] += in0 ? t0 : A(0);
+                acc[k] += in1 ? t1 : A(0);
+            }
+        }
+    }
+    if (L & 1) {  // odd last slot, stored plainly
+        const uint64_t e = (uint64_t)(j0 + L - 1) * kWave + lane;
+        const V v = __builtin_nontemporal_load(val + e);
+        const OS o = __builtin_nontemporal_load(off + e);
+        uint32_t b;
+        if constexpr (OB == 3) {
+            const uint32_t *bb = sbase + 4 * (j0 + L - 1);
+            const uint32_t k = o >> 14;
+            b = k == 0 ? bb[0] : k == 1 ? bb[1] : k == 2 ? bb[2] : bb[3];
+        } else {
+            b = sbase[j0 + L - 1];
+        }
+        const XT *g = reinterpret_cast<const XT *>(X + (uint64_t)(b + (OB == 3 ? (o & 0x3FFFu) : (uint32_t)o)) * K);
+        XT xv[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+            xv[c] = g[c];
+        const bool in = L - 1 < mylen;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const A t = A(v) * A(xv[k / CE][k % CE]);
+            acc[k] += in ? t : A(0);
+        }
+    }
+    if (row < nrows) {
+        XT *out = reinterpret_cast<XT *>(Y + (uint64_t)row * K);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            XT w;
+#pragma unroll
+            for (int i = 0; i < CE; ++i)
+                w[i] = V(acc[c * CE + i]);
+            out[c] = w;
+        }
+    }
+}
+
+template <typename A>
+static void launch_slices_multi_acc(const spmv_plan &p, int nvec, const ValueType *d_X, ValueType *d_Y, hipStream_t s,
+                                    bool warm)
+{
+    const uint32_t nsl = (uint32_t)p.nslices;
+    const dim3 grid((nsl + kSliceThreads / kWave - 1) / (kSliceThreads / kWave));
+#define SLM(OB, K)                                                                                               \
+    launch_or_warm(warm, k_spmv_slices_multi<ValueType, OB, K, multi_pairs(K), A>, grid, dim3(kSliceThreads), 0, \
+                   s, (const ValueType *)p.d_val, (const void *)p.d_colnar, (const uint32_t *)p.d_sbase,         \
+                   (const uint32_t *)p.d_slot_off, (const uint32_t *)p.d_slice_len, d_X, d_Y, p.nr_rows, nsl)
+#define SLK(OB)                                                                                                  \
+    do {                                                                                                         \
+        if (nvec == 2)                                                                                           \
+            SLM(OB, 2);                                                                                          \
+        else if (nvec == 4)                                                                                      \
+            SLM(OB, 4);                                                                                          \
+        else                                                                                                     \
+            SLM(OB, 8);                                                                                          \
+    } while (0)
+    if (p.slice_off_bytes == 1)
+        SLK(1);
+    else if (p.slice_off_bytes == 2 && p.slice_clustered)
+        SLK(3);
+    else if (p.slice_off_bytes == 2)
+        SLK(2);
+    else
+        SLK(4);
+#undef SLK
+#undef SLM
+}
+
+// d_Y[nr_rows x nvec] = A * d_X[nr_cols x nvec], both row-major; nvec is 2, 4 or 8 and the plan a
+// slice plan (multi.cpp checks both)
+hipError_t launch_slices_multi(const spmv_plan &p, int nvec, const ValueType *d_X, ValueType *d_Y, hipStream_t s,
+                               bool warm)
+{
+    if (p.kernel != kKernelSlices || (nvec != 2 && nvec != 4 && nvec != 8))
+        return hipErrorInvalidValue;
+    if (p.nr_rows == 0)
+        return hipSuccess;
+    if constexpr (sizeof(ValueType) == 4) {
+        if (p.slice_acc_native) {  // fp32 accumulator (env SPMV_SLICE_ACC=32)
+            launch_slices_multi_acc<ValueType>(p, nvec, d_X, d_Y, s, warm);
+            return hipGetLastError();
+        }
+    }
+    launch_slices_multi_acc<double>(p, nvec, d_X, d_Y, s, warm);
+    return hipGetLastError();
+}
+
 hipError_t launch_slices(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm)
 {
     if (p.nr_rows == 0)

@@ -271,6 +271,9 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
 hipError_t launch_slices(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm = false);
 int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, const ValueType *d_val_src,
                  hipStream_t s);
+// K = nvec (2, 4 or 8) right-hand sides in one pass over a slice plan; X and Y row-major
+hipError_t launch_slices_multi(const spmv_plan &p, int nvec, const ValueType *d_X, ValueType *d_Y, hipStream_t s,
+                               bool warm = false);
 
 // binned.hip
 hipError_t launch_binned(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm = false);
@@ -308,7 +311,8 @@ int upload_staged(void *dst, const void *src, size_t bytes, hipStream_t s);  // 
 int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows, IndexType nr_cols,
                                  const IndexType *h_row_ptr /* rebased, nr_rows+1 */,
                                  const IndexType *col_src, const ValueType *val_src,
-                                 bool src_on_device, hipStream_t s);
+                                 bool src_on_device, hipStream_t s, int force_kernel = -1);
+// force_kernel >= 0: that kernel as if env SPMV_HW_KERNEL named it (spmv_multi's native path)
 
 // mgpu.cpp helpers for spmv_hw's RCCL merge (csr_hw_wrapper.cpp): a clique over n distinct
 // devices (one rank each, ncclCommInitAll) that borrows the units' plans and takes each device's

@@ -98,6 +98,16 @@ class spmv_plan_stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class spmv_multi_stats(ctypes.Structure):
+    _fields_ = [("nr_rows", ctypes.c_uint64), ("nr_cols", ctypes.c_uint64), ("nr_nzeros", ctypes.c_uint64),
+                ("device_bytes", ctypes.c_uint64), ("algorithmic_bytes", ctypes.c_uint64),
+                ("device", ctypes.c_int32), ("nvec", ctypes.c_int32), ("native", ctypes.c_int32),
+                ("kernel", ctypes.c_int32), ("format", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/csr_hw_wrapper.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "create_csr_hw_matrix", "create_csr_hw_y_vector", "create_csr_hw_x_vector", "spmv_hw",
@@ -106,6 +116,8 @@ EXPORTS = [
     "spmv_hw_units", "spmv_hw_set_units", "spmv_hw_value_bytes", "spmv_hw_last_error",
     "spmv_plan_create_device", "spmv_plan_create_host", "spmv_plan_run", "spmv_plan_run_graph", "spmv_plan_get_stats",
     "spmv_plan_set_variant", "spmv_plan_set_timing", "spmv_plan_get_timing", "spmv_plan_destroy", "spmv_partition_rows",
+    "spmv_multi_create_device", "spmv_multi_create_host", "spmv_multi_run", "spmv_multi_get_stats",
+    "spmv_multi_destroy",
     "spmv_gen_banded", "spmv_gen_powerlaw_row_ptr", "spmv_gen_fill", "spmv_gen_vector",
     "spmv_read_csr_header", "spmv_read_csr_matrix", "spmv_read_csr", "spmv_free_csr",
     "spmv_mgpu_create", "spmv_mgpu_set_x", "spmv_mgpu_run", "spmv_mgpu_get_y", "spmv_mgpu_get_timing",
@@ -170,6 +182,14 @@ class Lib:
             "spmv_plan_get_timing": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double),
                                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
             "spmv_plan_destroy": (None, [vp]),
+            "spmv_multi_create_device": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, IndexType, IndexType,
+                                                        IndexType, vp, vp, vp, ctypes.c_int, vp]),
+            "spmv_multi_create_host": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int,
+                                                      ctypes.POINTER(self.csr_matrix), IndexType, IndexType,
+                                                      ctypes.c_int]),
+            "spmv_multi_run": (ctypes.c_int, [vp, vp, vp, vp]),
+            "spmv_multi_get_stats": (ctypes.c_int, [vp, ctypes.POINTER(spmv_multi_stats)]),
+            "spmv_multi_destroy": (None, [vp]),
             "spmv_partition_rows": (ctypes.c_int, [up, IndexType, ctypes.c_int, up]),
             "spmv_gen_banded": (ctypes.c_int, [IndexType, IndexType, ctypes.c_uint64, vp, vp, vp, vp]),
             "spmv_gen_powerlaw_row_ptr": (ctypes.c_int, [IndexType, ctypes.c_uint64, IndexType, ctypes.c_uint64,
@@ -397,6 +417,62 @@ class Plan:
     def destroy(self) -> None:
         if self.h:
             self.lib.L.spmv_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class MultiPlan:
+    """Y = A X for `nvec` (1..8) right-hand sides per run (spmv_multi_*, include/csr_hw_wrapper.h):
+    X is a contiguous (nr_cols, nvec) tensor, Y a contiguous (nr_rows, nvec) one. stats()["native"]
+    tells whether the one-pass slice kernel or the per-vector fallback runs."""
+
+    def __init__(self, lib: Lib, handle: ctypes.c_void_p, nr_rows: int, nr_cols: int, nvec: int):
+        self.lib = lib
+        self.h = handle
+        self.nr_rows, self.nr_cols, self.nvec = int(nr_rows), int(nr_cols), int(nvec)
+
+    @classmethod
+    def from_device(cls, lib: Lib, row_ptr, col, val, nr_cols: int, nvec: int, device: int = 0, stream=None):
+        """row_ptr/col/val: torch tensors on `device` (uint32 viewed as int32, values of lib.dtype)."""
+        h = ctypes.c_void_p()
+        n = row_ptr.numel() - 1
+        nnz = int(row_ptr[-1].item()) - int(row_ptr[0].item()) if n >= 0 else 0
+        lib._ok(lib.L.spmv_multi_create_device(ctypes.byref(h), device, n, nr_cols, nnz & 0xFFFFFFFF,
+                                               row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), int(nvec),
+                                               _stream_ptr(stream)), "spmv_multi_create_device")
+        return cls(lib, h, n, nr_cols, nvec)
+
+    @classmethod
+    def from_host(cls, lib: Lib, matrix, row_begin: int, row_end: int, nvec: int, device: int = 0):
+        h = ctypes.c_void_p()
+        lib._ok(lib.L.spmv_multi_create_host(ctypes.byref(h), device, ctypes.byref(matrix), row_begin, row_end,
+                                             int(nvec)), "spmv_multi_create_host")
+        return cls(lib, h, row_end - row_begin, int(matrix.nr_cols), nvec)
+
+    def run(self, X, Y, stream=None) -> None:
+        for name, t, n in (("X", X, self.nr_cols), ("Y", Y, self.nr_rows)):
+            if tuple(t.shape) != (n, self.nvec):
+                raise ValueError(f"MultiPlan.run: {name} has shape {tuple(t.shape)}, expected {(n, self.nvec)}")
+            if t.dtype != _torch_dtype(self.lib.dtype):
+                raise ValueError(f"MultiPlan.run: {name} is {t.dtype}, the library is {self.lib.dtype}")
+            if not t.is_contiguous():
+                raise ValueError(f"MultiPlan.run: {name} is not contiguous")
+        self.lib._ok(self.lib.L.spmv_multi_run(self.h, X.data_ptr(), Y.data_ptr(), _stream_ptr(stream)),
+                     "spmv_multi_run")
+
+    def stats(self) -> dict:
+        st = spmv_multi_stats()
+        self.lib._ok(self.lib.L.spmv_multi_get_stats(self.h, ctypes.byref(st)), "spmv_multi_get_stats")
+        return st.as_dict()
+
+    def destroy(self) -> None:
+        if self.h:
+            self.lib.L.spmv_multi_destroy(self.h)
             self.h = None
 
     def __del__(self):  # pragma: no cover
