@@ -130,6 +130,44 @@ int spmv_plan_create_device(spmv_plan **plan, int device, uint32_t nr_rows, uint
 /* Build a plan from rows [row_begin, row_end) of a host CSR matrix. */
 int spmv_plan_create_host(spmv_plan **plan, int device, const csr_matrix *matrix,
                           uint32_t row_begin, uint32_t row_end);
+/* Transposed plans. op = SPMV_OP_N is exactly spmv_plan_create_device / _host. op = SPMV_OP_T
+ * builds the plan of A^T, A being the slice the other arguments describe (they keep A's meaning:
+ * nr_rows, nr_cols, row_ptr of A): the slice is taken to the device (the host form uploads it),
+ * transposed there by spmv_csr_transpose_device's code, and the result goes through the same plan
+ * construction. The plan is an ordinary plan of a nr_cols x nr_rows matrix: spmv_plan_run reads a
+ * d_x of A's nr_rows values and writes a d_y of A's nr_cols values; kernel choice, env
+ * SPMV_HW_KERNEL, run_graph, set_variant, timing and the multi-vector forms apply unchanged, and
+ * spmv_plan_get_stats reports A^T's shape (nr_rows = A's nr_cols, nr_cols = the slice's rows).
+ * A^T's rows list A's entries of one column in A's CSR order, so the bitwise spmv_gold modes
+ * (gold kernel, fp64 slices) are bitwise spmv_gold of that transposed CSR. At most 2^31 - 1
+ * non-zeros per transposed slice. Any other op returns nonzero ("op must be ...") before any
+ * HIP call. Not for spmv_mgpu_* slices (a row-sliced A^T gives full-length partials) nor Part 1. */
+#define SPMV_OP_N 0
+#define SPMV_OP_T 1
+int spmv_plan_create_device_op(spmv_plan **plan, int device, int op, uint32_t nr_rows, uint32_t nr_cols,
+                               uint32_t nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col_ind,
+                               const ValueType *d_values, void *stream);
+int spmv_plan_create_host_op(spmv_plan **plan, int device, int op, const csr_matrix *matrix,
+                             uint32_t row_begin, uint32_t row_end);
+/* *op = SPMV_OP_N or SPMV_OP_T, as the plan was created. */
+int spmv_plan_get_op(const spmv_plan *plan, int *op);
+/* A^T of a device-resident CSR slice (nr_rows x nr_cols, d_row_ptr may start at any offset, as
+ * for spmv_plan_create_device), as CSR: d_t_row_ptr[nr_cols + 1] starts at 0, d_t_col_ind[nnz]
+ * holds slice-local source rows (0 .. nr_rows - 1), d_t_values[nnz] the values; the caller owns
+ * all three (the entry arrays may be null when the slice has no non-zeros; none may overlap an
+ * input: d_t_col_ind doubles as the sort's scratch).
+ *   Stable: row c of A^T lists the entries of column c of A in A's CSR entry order, so its column
+ *     indices do not decrease; duplicate (r, c) entries are kept in order; the columns inside a
+ *     row of A need not be sorted.
+ *   Deterministic: the same input gives the same three arrays bit for bit on every run.
+ *   Column indices >= nr_cols are refused ("column index out of range"). More than 2^31 - 1
+ *     non-zeros are refused, after row_ptr was read and before d_col_ind or d_values is touched.
+ *   Only row_ptr crosses to the host. The call returns when the work has completed on `stream`;
+ *     its temporaries (12 bytes per non-zero, nr_rows + 1 words and the radix sort's workspace)
+ *     are freed by then. */
+int spmv_csr_transpose_device(int device, uint32_t nr_rows, uint32_t nr_cols, uint32_t nr_nzeros,
+                              const IndexType *d_row_ptr, const IndexType *d_col_ind, const ValueType *d_values,
+                              IndexType *d_t_row_ptr, IndexType *d_t_col_ind, ValueType *d_t_values, void *stream);
 /* d_y[0:nr_rows) = A * d_x  (overwrite; empty rows get 0). Asynchronous on `stream`. Enqueues
  * only kernels and memsets (when timing is off), so callers may capture it into their own
  * hipGraph, e.g. an iterative solver's SpMV + update + RCCL all-gather step.
@@ -194,6 +232,14 @@ int spmv_multi_create_device(spmv_multi **m, int device, uint32_t nr_rows, uint3
                              const ValueType *d_values, int nvec, void *stream);
 int spmv_multi_create_host(spmv_multi **m, int device, const csr_matrix *matrix,
                            uint32_t row_begin, uint32_t row_end, int nvec);
+/* The same with an op (SPMV_OP_N / SPMV_OP_T, as spmv_plan_create_device_op): op = T gives
+ * Y = A^T * X, d_X being (the slice's rows) x nvec and d_Y (A's nr_cols) x nvec; the stats report
+ * A^T's shape. A bad op returns nonzero before any HIP call. */
+int spmv_multi_create_device_op(spmv_multi **m, int device, int op, uint32_t nr_rows, uint32_t nr_cols,
+                                uint32_t nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col_ind,
+                                const ValueType *d_values, int nvec, void *stream);
+int spmv_multi_create_host_op(spmv_multi **m, int device, int op, const csr_matrix *matrix,
+                              uint32_t row_begin, uint32_t row_end, int nvec);
 int spmv_multi_run(const spmv_multi *m, const ValueType *d_X, ValueType *d_Y, void *stream);
 int spmv_multi_get_stats(const spmv_multi *m, spmv_multi_stats *stats);
 void spmv_multi_destroy(spmv_multi *m);

@@ -124,6 +124,20 @@ static int multi_create(spmv_multi **out, int device, IndexType nr_rows, IndexTy
     return 0;
 }
 
+// op = T: the slice's transpose (transpose.hip), then the same decision and build on A^T
+static int multi_create_transposed(spmv_multi **out, int device, IndexType n, IndexType m, const IndexType *rp,
+                                   const IndexType *col, const ValueType *val, bool on_device, int nvec, hipStream_t s)
+{
+    SPMV_TRY(hipSetDevice(device));
+    transposed_csr t;
+    if (transpose_slice(t, n, m, rp, col, val, on_device, s))
+        return 1;
+    if (multi_create(out, device, m, n, t.rp.data(), t.d_col, t.d_val, true, nvec, s))
+        return 1;
+    (*out)->plan->op = SPMV_OP_T;
+    return 0;
+}
+
 static bool multi_bad_nvec(const char *who, int nvec)
 {
     if (nvec >= 1 && nvec <= 8)
@@ -182,6 +196,63 @@ int spmv_multi_create_host(spmv_multi **m, int device, const csr_matrix *mat, In
         rp[r] = mat->row_ptr[row_begin + r] - base;
     return multi_create(m, device, n, mat->nr_cols, rp.data(), mat->col_ind + base, mat->values + base, false, nvec,
                         nullptr);
+}
+
+int spmv_multi_create_device_op(spmv_multi **m, int device, int op, IndexType nr_rows, IndexType nr_cols,
+                                IndexType nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col_ind,
+                                const ValueType *d_values, int nvec, void *stream)
+{
+    if (bad_op("spmv_multi_create_device_op", op))
+        return 1;
+    if (op == SPMV_OP_N)
+        return spmv_multi_create_device(m, device, nr_rows, nr_cols, nr_nzeros, d_row_ptr, d_col_ind, d_values, nvec,
+                                        stream);
+    if (!m || (nr_rows && !d_row_ptr)) {
+        set_error("spmv_multi_create_device_op: null argument");
+        return 1;
+    }
+    *m = nullptr;
+    if (multi_bad_nvec("spmv_multi_create_device_op", nvec))
+        return 1;
+    hipStream_t s = (hipStream_t)stream;
+    SPMV_TRY(hipSetDevice(device));
+    std::vector<IndexType> rp(size_t(nr_rows) + 1, 0u);
+    if (nr_rows) {
+        SPMV_TRY(hipMemcpyAsync(rp.data(), d_row_ptr, rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
+        SPMV_TRY(hipStreamSynchronize(s));
+    }
+    const IndexType base = rp[0];
+    for (auto &e : rp)
+        e -= base;
+    if (rp[nr_rows] != nr_nzeros) {
+        set_error("spmv_multi_create_device_op: row_ptr[n]-row_ptr[0] != nr_nzeros");
+        return 1;
+    }
+    return multi_create_transposed(m, device, nr_rows, nr_cols, rp.data(), d_col_ind ? d_col_ind + base : nullptr,
+                                   d_values ? d_values + base : nullptr, true, nvec, s);
+}
+
+int spmv_multi_create_host_op(spmv_multi **m, int device, int op, const csr_matrix *mat, IndexType row_begin,
+                              IndexType row_end, int nvec)
+{
+    if (bad_op("spmv_multi_create_host_op", op))
+        return 1;
+    if (op == SPMV_OP_N)
+        return spmv_multi_create_host(m, device, mat, row_begin, row_end, nvec);
+    if (!m || !mat || row_begin > row_end || row_end > mat->nr_rows) {
+        set_error("spmv_multi_create_host_op: bad arguments");
+        return 1;
+    }
+    *m = nullptr;
+    if (multi_bad_nvec("spmv_multi_create_host_op", nvec))
+        return 1;
+    const IndexType n = row_end - row_begin;
+    const IndexType base = mat->row_ptr[row_begin];
+    std::vector<IndexType> rp(size_t(n) + 1);
+    for (IndexType r = 0; r <= n; ++r)
+        rp[r] = mat->row_ptr[row_begin + r] - base;
+    return multi_create_transposed(m, device, n, mat->nr_cols, rp.data(), mat->col_ind + base, mat->values + base,
+                                   false, nvec, nullptr);
 }
 
 int spmv_multi_run(const spmv_multi *m, const ValueType *d_X, ValueType *d_Y, void *stream)

@@ -817,6 +817,83 @@ int spmv_plan_create_host(spmv_plan **plan, int device, const csr_matrix *m, Ind
                                         m->values + base, false, s);
 }
 
+// op = T: the slice's transpose (transpose.hip) through the same plan construction, n x m -> m x n
+static int plan_create_transposed(spmv_plan **plan, int device, IndexType n, IndexType m, const IndexType *h_rp,
+                                  const IndexType *col_src, const ValueType *val_src, bool src_on_device,
+                                  hipStream_t s)
+{
+    *plan = nullptr;
+    SPMV_TRY(hipSetDevice(device));
+    transposed_csr t;
+    if (transpose_slice(t, n, m, h_rp, col_src, val_src, src_on_device, s))
+        return 1;
+    if (plan_create_from_host_rowptr(plan, device, m, n, t.rp.data(), t.d_col, t.d_val, true, s))
+        return 1;
+    (*plan)->op = SPMV_OP_T;
+    return 0;
+}
+
+int spmv_plan_create_device_op(spmv_plan **plan, int device, int op, IndexType nr_rows, IndexType nr_cols,
+                               IndexType nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col_ind,
+                               const ValueType *d_values, void *stream)
+{
+    if (bad_op("spmv_plan_create_device_op", op))
+        return 1;
+    if (op == SPMV_OP_N)
+        return spmv_plan_create_device(plan, device, nr_rows, nr_cols, nr_nzeros, d_row_ptr, d_col_ind, d_values,
+                                       stream);
+    if (!plan || (nr_rows && !d_row_ptr)) {
+        set_error("spmv_plan_create_device_op: null argument");
+        return 1;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SPMV_TRY(hipSetDevice(device));
+    std::vector<IndexType> rp(size_t(nr_rows) + 1, 0u);
+    if (nr_rows) {
+        SPMV_TRY(hipMemcpyAsync(rp.data(), d_row_ptr, rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
+        SPMV_TRY(hipStreamSynchronize(s));
+    }
+    const IndexType base = rp[0];
+    for (auto &e : rp)
+        e -= base;
+    if (rp[nr_rows] != nr_nzeros) {
+        set_error("spmv_plan_create_device_op: row_ptr[n]-row_ptr[0] != nr_nzeros");
+        return 1;
+    }
+    return plan_create_transposed(plan, device, nr_rows, nr_cols, rp.data(), d_col_ind ? d_col_ind + base : nullptr,
+                                  d_values ? d_values + base : nullptr, true, s);
+}
+
+int spmv_plan_create_host_op(spmv_plan **plan, int device, int op, const csr_matrix *m, IndexType row_begin,
+                             IndexType row_end)
+{
+    if (bad_op("spmv_plan_create_host_op", op))
+        return 1;
+    if (op == SPMV_OP_N)
+        return spmv_plan_create_host(plan, device, m, row_begin, row_end);
+    if (!plan || !m || row_begin > row_end || row_end > m->nr_rows) {
+        set_error("spmv_plan_create_host_op: bad arguments");
+        return 1;
+    }
+    const IndexType n = row_end - row_begin;
+    const IndexType base = m->row_ptr[row_begin];
+    std::vector<IndexType> rp(size_t(n) + 1);
+    for (IndexType r = 0; r <= n; ++r)
+        rp[r] = m->row_ptr[row_begin + r] - base;
+    return plan_create_transposed(plan, device, n, m->nr_cols, rp.data(), m->col_ind + base, m->values + base, false,
+                                  nullptr);
+}
+
+int spmv_plan_get_op(const spmv_plan *plan, int *op)
+{
+    if (!plan || !op) {
+        set_error("spmv_plan_get_op: null argument");
+        return 1;
+    }
+    *op = plan->op;
+    return 0;
+}
+
 // Enqueues one SpMV (memset of y when rows can be empty, main kernel, tile fix-up) on s. Only
 // kernels and memsets are enqueued, so the sequence is capturable into a hipGraph.
 static int run_impl(spmv_plan *p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool timing)

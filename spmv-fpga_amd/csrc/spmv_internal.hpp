@@ -82,6 +82,7 @@ struct spmv_plan {
     uint64_t ntiles = 0;
     bool has_empty = false;
     int kernel = 0;
+    int op = SPMV_OP_N;        // SPMV_OP_T: the plan holds A^T of the slice it was created from
     int variant = 0;           // tile-kernel variant bits (spmv_plan_set_variant)
     int sweep_variant = 28;    // sweep-kernel variant bits (spmv_plan_set_variant, kernel 2)
 
@@ -313,6 +314,27 @@ int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows,
                                  const IndexType *col_src, const ValueType *val_src,
                                  bool src_on_device, hipStream_t s, int force_kernel = -1);
 // force_kernel >= 0: that kernel as if env SPMV_HW_KERNEL named it (spmv_multi's native path)
+
+// transpose.hip
+bool bad_op(const char *who, int op);  // true (and the error set) unless op is SPMV_OP_N or SPMV_OP_T
+int check_transpose_size(const char *who, uint64_t nnz);  // nonzero (error set) above 2^31 - 1 non-zeros
+// A^T of an n x m CSR slice on the device, stable and deterministic. h_rp: the
+// slice's row_ptr on the host, rebased to 0 and non-decreasing; d_col / d_val: its entries on the
+// device (only read). Writes d_t_rp[m + 1], d_t_col[nnz] (slice-local source rows), d_t_val[nnz];
+// returns once the work has completed on s, its temporaries freed.
+int csr_transpose_device(IndexType n, IndexType m, const IndexType *h_rp, const IndexType *d_col,
+                         const ValueType *d_val, IndexType *d_t_rp, IndexType *d_t_col, ValueType *d_t_val,
+                         hipStream_t s);
+// A^T of a slice as the create functions take it: row_ptr on the host, entries on the device
+struct transposed_csr {
+    std::vector<IndexType> rp;  // m + 1, starts at 0
+    IndexType *d_col = nullptr;
+    ValueType *d_val = nullptr;
+    ~transposed_csr();
+};
+// col_src / val_src on the host (uploaded first) or the device; checks h_rp and the size limit
+int transpose_slice(transposed_csr &t, IndexType n, IndexType m, const IndexType *h_rp, const IndexType *col_src,
+                    const ValueType *val_src, bool src_on_device, hipStream_t s);
 
 // mgpu.cpp helpers for spmv_hw's RCCL merge (csr_hw_wrapper.cpp): a clique over n distinct
 // devices (one rank each, ncclCommInitAll) that borrows the units' plans and takes each device's

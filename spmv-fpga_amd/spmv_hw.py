@@ -118,6 +118,8 @@ EXPORTS = [
     "spmv_plan_set_variant", "spmv_plan_set_timing", "spmv_plan_get_timing", "spmv_plan_destroy", "spmv_partition_rows",
     "spmv_multi_create_device", "spmv_multi_create_host", "spmv_multi_run", "spmv_multi_get_stats",
     "spmv_multi_destroy",
+    "spmv_plan_create_device_op", "spmv_plan_create_host_op", "spmv_plan_get_op", "spmv_csr_transpose_device",
+    "spmv_multi_create_device_op", "spmv_multi_create_host_op",
     "spmv_gen_banded", "spmv_gen_powerlaw_row_ptr", "spmv_gen_fill", "spmv_gen_vector",
     "spmv_read_csr_header", "spmv_read_csr_matrix", "spmv_read_csr", "spmv_free_csr",
     "spmv_mgpu_create", "spmv_mgpu_set_x", "spmv_mgpu_run", "spmv_mgpu_get_y", "spmv_mgpu_get_timing",
@@ -126,6 +128,7 @@ EXPORTS = [
     "spmv_mgpu_run_graph", "spmv_mgpu_comm_count", "spmv_mgpu_schedule",
 ]
 
+OP_N, OP_T = 0, 1  # include/csr_hw_wrapper.h SPMV_OP_*
 MGPU_GATHER, MGPU_REDUCE, MGPU_ALLGATHER = 0, 1, 2  # include/csr_hw_wrapper.h SPMV_MGPU_*
 # spmv_xop kinds and buffers (include/csr_hw_wrapper.h SPMV_XOP_* / SPMV_XBUF_*)
 XOP_ZERO, XOP_COMPUTE, XOP_SEND, XOP_RECV, XOP_REDUCE, XOP_BCAST = range(6)
@@ -190,6 +193,18 @@ class Lib:
             "spmv_multi_run": (ctypes.c_int, [vp, vp, vp, vp]),
             "spmv_multi_get_stats": (ctypes.c_int, [vp, ctypes.POINTER(spmv_multi_stats)]),
             "spmv_multi_destroy": (None, [vp]),
+            "spmv_plan_create_device_op": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, IndexType,
+                                                          IndexType, IndexType, vp, vp, vp, vp]),
+            "spmv_plan_create_host_op": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int,
+                                                        ctypes.POINTER(self.csr_matrix), IndexType, IndexType]),
+            "spmv_plan_get_op": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int)]),
+            "spmv_csr_transpose_device": (ctypes.c_int, [ctypes.c_int, IndexType, IndexType, IndexType, vp, vp, vp,
+                                                         vp, vp, vp, vp]),
+            "spmv_multi_create_device_op": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, IndexType,
+                                                           IndexType, IndexType, vp, vp, vp, ctypes.c_int, vp]),
+            "spmv_multi_create_host_op": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int,
+                                                         ctypes.POINTER(self.csr_matrix), IndexType, IndexType,
+                                                         ctypes.c_int]),
             "spmv_partition_rows": (ctypes.c_int, [up, IndexType, ctypes.c_int, up]),
             "spmv_gen_banded": (ctypes.c_int, [IndexType, IndexType, ctypes.c_uint64, vp, vp, vp, vp]),
             "spmv_gen_powerlaw_row_ptr": (ctypes.c_int, [IndexType, ctypes.c_uint64, IndexType, ctypes.c_uint64,
@@ -371,22 +386,41 @@ class Plan:
         self.h = handle
 
     @classmethod
-    def from_device(cls, lib: Lib, row_ptr, col, val, nr_cols: int, device: int = 0, stream=None):
-        """row_ptr/col/val: torch tensors on `device` (uint32 viewed as int32, values of lib.dtype)."""
+    def from_device(cls, lib: Lib, row_ptr, col, val, nr_cols: int, device: int = 0, stream=None,
+                    transpose: bool = False):
+        """row_ptr/col/val: torch tensors on `device` (uint32 viewed as int32, values of lib.dtype).
+        transpose=True builds the plan of A^T (spmv_plan_create_device_op, SPMV_OP_T): run() then
+        takes an x of A's rows and writes a y of nr_cols values."""
         h = ctypes.c_void_p()
         n = row_ptr.numel() - 1
         nnz = int(row_ptr[-1].item()) - int(row_ptr[0].item()) if n >= 0 else 0
+        if transpose:
+            lib._ok(lib.L.spmv_plan_create_device_op(ctypes.byref(h), device, OP_T, n, nr_cols, nnz & 0xFFFFFFFF,
+                                                     row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(),
+                                                     _stream_ptr(stream)), "spmv_plan_create_device_op")
+            return cls(lib, h)
         lib._ok(lib.L.spmv_plan_create_device(ctypes.byref(h), device, n, nr_cols, nnz & 0xFFFFFFFF,
                                               row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(),
                                               _stream_ptr(stream)), "spmv_plan_create_device")
         return cls(lib, h)
 
     @classmethod
-    def from_host(cls, lib: Lib, matrix, row_begin: int, row_end: int, device: int = 0):
+    def from_host(cls, lib: Lib, matrix, row_begin: int, row_end: int, device: int = 0, transpose: bool = False):
         h = ctypes.c_void_p()
+        if transpose:
+            lib._ok(lib.L.spmv_plan_create_host_op(ctypes.byref(h), device, OP_T, ctypes.byref(matrix), row_begin,
+                                                   row_end), "spmv_plan_create_host_op")
+            return cls(lib, h)
         lib._ok(lib.L.spmv_plan_create_host(ctypes.byref(h), device, ctypes.byref(matrix), row_begin, row_end),
                 "spmv_plan_create_host")
         return cls(lib, h)
+
+    @property
+    def op(self) -> int:
+        """OP_N (0) or OP_T (1): whether the plan multiplies by A or by A^T (spmv_plan_get_op)."""
+        v = ctypes.c_int(-1)
+        self.lib._ok(self.lib.L.spmv_plan_get_op(self.h, ctypes.byref(v)), "spmv_plan_get_op")
+        return int(v.value)
 
     def run(self, x, y, stream=None) -> None:
         self.lib._ok(self.lib.L.spmv_plan_run(self.h, x.data_ptr(), y.data_ptr(), _stream_ptr(stream)),
@@ -431,25 +465,37 @@ class MultiPlan:
     X is a contiguous (nr_cols, nvec) tensor, Y a contiguous (nr_rows, nvec) one. stats()["native"]
     tells whether the one-pass slice kernel or the per-vector fallback runs."""
 
-    def __init__(self, lib: Lib, handle: ctypes.c_void_p, nr_rows: int, nr_cols: int, nvec: int):
+    def __init__(self, lib: Lib, handle: ctypes.c_void_p, nr_rows: int, nr_cols: int, nvec: int, op: int = OP_N):
         self.lib = lib
         self.h = handle
-        self.nr_rows, self.nr_cols, self.nvec = int(nr_rows), int(nr_cols), int(nvec)
+        self.nr_rows, self.nr_cols, self.nvec, self.op = int(nr_rows), int(nr_cols), int(nvec), int(op)
 
     @classmethod
-    def from_device(cls, lib: Lib, row_ptr, col, val, nr_cols: int, nvec: int, device: int = 0, stream=None):
-        """row_ptr/col/val: torch tensors on `device` (uint32 viewed as int32, values of lib.dtype)."""
+    def from_device(cls, lib: Lib, row_ptr, col, val, nr_cols: int, nvec: int, device: int = 0, stream=None,
+                    transpose: bool = False):
+        """row_ptr/col/val: torch tensors on `device` (uint32 viewed as int32, values of lib.dtype).
+        transpose=True: Y = A^T X, X of shape (A's rows, nvec) and Y of shape (nr_cols, nvec)."""
         h = ctypes.c_void_p()
         n = row_ptr.numel() - 1
         nnz = int(row_ptr[-1].item()) - int(row_ptr[0].item()) if n >= 0 else 0
+        if transpose:
+            lib._ok(lib.L.spmv_multi_create_device_op(ctypes.byref(h), device, OP_T, n, nr_cols, nnz & 0xFFFFFFFF,
+                                                      row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), int(nvec),
+                                                      _stream_ptr(stream)), "spmv_multi_create_device_op")
+            return cls(lib, h, nr_cols, n, nvec, OP_T)
         lib._ok(lib.L.spmv_multi_create_device(ctypes.byref(h), device, n, nr_cols, nnz & 0xFFFFFFFF,
                                                row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), int(nvec),
                                                _stream_ptr(stream)), "spmv_multi_create_device")
         return cls(lib, h, n, nr_cols, nvec)
 
     @classmethod
-    def from_host(cls, lib: Lib, matrix, row_begin: int, row_end: int, nvec: int, device: int = 0):
+    def from_host(cls, lib: Lib, matrix, row_begin: int, row_end: int, nvec: int, device: int = 0,
+                  transpose: bool = False):
         h = ctypes.c_void_p()
+        if transpose:
+            lib._ok(lib.L.spmv_multi_create_host_op(ctypes.byref(h), device, OP_T, ctypes.byref(matrix), row_begin,
+                                                    row_end, int(nvec)), "spmv_multi_create_host_op")
+            return cls(lib, h, int(matrix.nr_cols), row_end - row_begin, nvec, OP_T)
         lib._ok(lib.L.spmv_multi_create_host(ctypes.byref(h), device, ctypes.byref(matrix), row_begin, row_end,
                                              int(nvec)), "spmv_multi_create_host")
         return cls(lib, h, row_end - row_begin, int(matrix.nr_cols), nvec)
@@ -596,6 +642,28 @@ def _stream_ptr(stream):
             return torch.cuda.current_stream().cuda_stream
         return None
     return getattr(stream, "cuda_stream", stream)
+
+
+TRANSPOSE_MAX_NNZ = 2 ** 31 - 1  # spmv_csr_transpose_device's limit per call
+
+
+def csr_transpose(lib: Lib, row_ptr, col, val, nr_cols: int, device: int = 0, stream=None):
+    """A^T of a device CSR (spmv_csr_transpose_device): row_ptr/col/val torch tensors on `device`
+    as for Plan.from_device (row_ptr may start at any offset). Returns (t_row_ptr[nr_cols + 1],
+    t_col[nnz], t_val[nnz]) as new tensors: stable (row c lists column c's entries in A's CSR
+    order; t_col are the slice-local source rows) and bitwise reproducible."""
+    n = row_ptr.numel() - 1
+    nnz = int(row_ptr[-1].item()) - int(row_ptr[0].item()) if n >= 0 else 0
+    nnz &= 0xFFFFFFFF
+    if nnz > TRANSPOSE_MAX_NNZ:  # before the outputs are allocated; the library refuses it the same way
+        raise RuntimeError("spmv_csr_transpose_device: the device transpose takes at most 2^31 - 1 non-zeros per call")
+    t_rp = torch.empty(int(nr_cols) + 1, dtype=torch.int32, device=row_ptr.device)
+    t_col = torch.empty(nnz, dtype=torch.int32, device=row_ptr.device)
+    t_val = torch.empty(nnz, dtype=_torch_dtype(lib.dtype), device=row_ptr.device)
+    lib._ok(lib.L.spmv_csr_transpose_device(device, max(n, 0), int(nr_cols), nnz, row_ptr.data_ptr(), col.data_ptr(),
+                                            val.data_ptr(), t_rp.data_ptr(), t_col.data_ptr(), t_val.data_ptr(),
+                                            _stream_ptr(stream)), "spmv_csr_transpose_device")
+    return t_rp, t_col, t_val
 
 
 def gen_banded(lib: Lib, n: int, width: int = 16, seed: int = 2, device: str = "cuda"):
