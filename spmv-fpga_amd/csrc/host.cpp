@@ -1,5 +1,5 @@
-// Host-only parts of libspmv_hw (no HIP calls): the error channel, the nnz-balanced row
-// partition, the exchange schedule of the multi-GPU merge, the threaded accum_results '+=',
+// Host-only parts of libspmv_hw (no HIP calls): the error channel, the CSR-slice front end of the
+// create calls (argument checks, rebased row_ptr), the nnz-balanced row partition, the exchange schedule of the multi-GPU merge, the threaded accum_results '+=',
 // verification and storage_overhead. Besides the product library, tests/sanitize/Makefile builds
 // this file and reader.cpp with g++ under AddressSanitizer + UBSan and under ThreadSanitizer
 // (SURVEY §5 "sanitizers").
@@ -27,6 +27,52 @@ double timestamp_us()
     struct timeval tv;
     gettimeofday(&tv, nullptr);
     return tv.tv_usec + tv.tv_sec * 1e6;
+}
+
+int slice_rebase(const char *who, csr_slice &s, const IndexType *nr_nzeros)
+{
+    const IndexType base = s.rp[0];
+    for (IndexType &e : s.rp)
+        e -= base;
+    if (nr_nzeros && s.rp[s.n] != *nr_nzeros) {
+        set_error(std::string(who) + ": row_ptr[n]-row_ptr[0] != nr_nzeros");
+        return 1;
+    }
+    if (s.col)
+        s.col += base;
+    if (s.val)
+        s.val += base;
+    for (IndexType r = 0; r < s.n; ++r)
+        if (s.rp[r + 1] < s.rp[r]) {
+            set_error("row_ptr is not non-decreasing at row " + std::to_string(r));
+            return 1;
+        }
+    return 0;
+}
+
+int slice_from_host(const char *who, csr_slice &out, const void *handle, const csr_matrix *m, IndexType row_begin,
+                    IndexType row_end)
+{
+    if (!handle || !m || row_begin > row_end || row_end > m->nr_rows) {
+        set_error(std::string(who) + ": bad arguments");
+        return 1;
+    }
+    out.n = row_end - row_begin;
+    out.m = m->nr_cols;
+    out.rp.assign(m->row_ptr + row_begin, m->row_ptr + row_end + 1);  // n + 1 entries, row_ptr[row_end] the last
+    out.col = m->col_ind;
+    out.val = m->values;
+    out.on_device = false;
+    out.stream = nullptr;
+    return slice_rebase(who, out);
+}
+
+int slice_device_args(const char *who, const void *handle, IndexType n, const IndexType *d_row_ptr)
+{
+    if (handle && (!n || d_row_ptr))
+        return 0;
+    set_error(std::string(who) + ": null argument");
+    return 1;
 }
 
 // Maps the caller's y pages writable while the DMA runs, keeping their contents: a fresh

@@ -83,10 +83,20 @@ static uint64_t slice_stored_entries(const IndexType *rp, IndexType n)
     return slots * kWave;
 }
 
-// rp: rebased host row_ptr. Decides the path, builds the plan and the fallback's scratch.
-static int multi_create(spmv_multi **out, int device, IndexType nr_rows, IndexType nr_cols, const IndexType *rp,
-                        const IndexType *col, const ValueType *val, bool on_device, int nvec, hipStream_t s)
+// Decides the path, builds the plan and the fallback's scratch. op = SPMV_OP_T: the slice's
+// transpose (transpose.hip), then the same decision and build on A^T.
+static int multi_create(spmv_multi **out, int device, int op, const csr_slice &sl, int nvec)
 {
+    if (op == SPMV_OP_T) {
+        SPMV_TRY(hipSetDevice(device));
+        transposed_csr t;
+        if (transpose_slice(t, sl) || multi_create(out, device, SPMV_OP_N, t.slice, nvec))
+            return 1;
+        (*out)->plan->op = SPMV_OP_T;
+        return 0;
+    }
+    const IndexType nr_rows = sl.n, nr_cols = sl.m;
+    hipStream_t s = (hipStream_t)sl.stream;
     const char *env = std::getenv("SPMV_HW_KERNEL");
     const bool automatic = !env || !*env || !std::strcmp(env, "auto");
     bool native = false;
@@ -94,15 +104,14 @@ static int multi_create(spmv_multi **out, int device, IndexType nr_rows, IndexTy
         if (env && !std::strcmp(env, "slices")) {
             native = true;
         } else if (automatic && nr_rows) {
-            const uint64_t nnz = rp[nr_rows], stored = slice_stored_entries(rp, nr_rows);
+            const uint64_t nnz = sl.nnz(), stored = slice_stored_entries(sl.rp.data(), nr_rows);
             native = nnz > 0 && stored <= 0xFFFFFFFFull && double(stored) <= multi_pad_limit(nvec) * double(nnz);
         }
     }
     std::unique_ptr<spmv_multi> m(new spmv_multi());
     m->nvec = nvec;
     m->native = native;
-    if (plan_create_from_host_rowptr(&m->plan, device, nr_rows, nr_cols, rp, col, val, on_device, s,
-                                     native ? kKernelSlices : -1))
+    if (plan_create_from_slice(&m->plan, device, SPMV_OP_N, sl, native ? kKernelSlices : -1))
         return 1;
     if (native && m->plan->kernel != kKernelSlices) {
         set_error("spmv_multi: internal: the native path needs a slice plan");
@@ -124,26 +133,41 @@ static int multi_create(spmv_multi **out, int device, IndexType nr_rows, IndexTy
     return 0;
 }
 
-// op = T: the slice's transpose (transpose.hip), then the same decision and build on A^T
-static int multi_create_transposed(spmv_multi **out, int device, IndexType n, IndexType m, const IndexType *rp,
-                                   const IndexType *col, const ValueType *val, bool on_device, int nvec, hipStream_t s)
-{
-    SPMV_TRY(hipSetDevice(device));
-    transposed_csr t;
-    if (transpose_slice(t, n, m, rp, col, val, on_device, s))
-        return 1;
-    if (multi_create(out, device, m, n, t.rp.data(), t.d_col, t.d_val, true, nvec, s))
-        return 1;
-    (*out)->plan->op = SPMV_OP_T;
-    return 0;
-}
-
 static bool multi_bad_nvec(const char *who, int nvec)
 {
     if (nvec >= 1 && nvec <= 8)
         return false;
     set_error(std::string(who) + ": nvec must be 1..8");
     return true;
+}
+
+// The four multi creates: `who` names the caller in the messages (op = SPMV_OP_N through an _op
+// function is the function without an op, and reports as it). nvec is checked after the other
+// arguments and before the first HIP call, which slice_from_device makes.
+static int create_device(const char *who, spmv_multi **m, int device, int op, IndexType nr_rows, IndexType nr_cols,
+                         IndexType nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col_ind,
+                         const ValueType *d_values, int nvec, void *stream)
+{
+    if (slice_device_args(who, m, nr_rows, d_row_ptr))
+        return 1;
+    *m = nullptr;
+    csr_slice sl;
+    if (multi_bad_nvec(who, nvec) || slice_from_device(who, sl, m, device, nr_rows, nr_cols, nr_nzeros, d_row_ptr,
+                                                       d_col_ind, d_values, (hipStream_t)stream))
+        return 1;
+    return multi_create(m, device, op, sl, nvec);
+}
+
+static int create_host(const char *who, spmv_multi **m, int device, int op, const csr_matrix *mat, IndexType row_begin,
+                       IndexType row_end, int nvec)
+{
+    csr_slice sl;
+    if (slice_from_host(who, sl, m, mat, row_begin, row_end))
+        return 1;
+    *m = nullptr;
+    if (multi_bad_nvec(who, nvec))
+        return 1;
+    return multi_create(m, device, op, sl, nvec);
 }
 
 }  // namespace spmvhw
@@ -154,48 +178,14 @@ int spmv_multi_create_device(spmv_multi **m, int device, IndexType nr_rows, Inde
                              const IndexType *d_row_ptr, const IndexType *d_col_ind, const ValueType *d_values,
                              int nvec, void *stream)
 {
-    if (!m || (nr_rows && !d_row_ptr)) {
-        set_error("spmv_multi_create_device: null argument");
-        return 1;
-    }
-    *m = nullptr;
-    if (multi_bad_nvec("spmv_multi_create_device", nvec))
-        return 1;
-    hipStream_t s = (hipStream_t)stream;
-    SPMV_TRY(hipSetDevice(device));
-    std::vector<IndexType> rp(size_t(nr_rows) + 1, 0u);
-    if (nr_rows) {
-        SPMV_TRY(hipMemcpyAsync(rp.data(), d_row_ptr, rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
-        SPMV_TRY(hipStreamSynchronize(s));
-    }
-    const IndexType base = rp[0];
-    for (auto &e : rp)
-        e -= base;
-    if (rp[nr_rows] != nr_nzeros) {
-        set_error("spmv_multi_create_device: row_ptr[n]-row_ptr[0] != nr_nzeros");
-        return 1;
-    }
-    return multi_create(m, device, nr_rows, nr_cols, rp.data(), d_col_ind ? d_col_ind + base : nullptr,
-                        d_values ? d_values + base : nullptr, true, nvec, s);
+    return create_device("spmv_multi_create_device", m, device, SPMV_OP_N, nr_rows, nr_cols, nr_nzeros, d_row_ptr,
+                         d_col_ind, d_values, nvec, stream);
 }
 
 int spmv_multi_create_host(spmv_multi **m, int device, const csr_matrix *mat, IndexType row_begin, IndexType row_end,
                            int nvec)
 {
-    if (!m || !mat || row_begin > row_end || row_end > mat->nr_rows) {
-        set_error("spmv_multi_create_host: bad arguments");
-        return 1;
-    }
-    *m = nullptr;
-    if (multi_bad_nvec("spmv_multi_create_host", nvec))
-        return 1;
-    const IndexType n = row_end - row_begin;
-    const IndexType base = mat->row_ptr[row_begin];
-    std::vector<IndexType> rp(size_t(n) + 1);
-    for (IndexType r = 0; r <= n; ++r)
-        rp[r] = mat->row_ptr[row_begin + r] - base;
-    return multi_create(m, device, n, mat->nr_cols, rp.data(), mat->col_ind + base, mat->values + base, false, nvec,
-                        nullptr);
+    return create_host("spmv_multi_create_host", m, device, SPMV_OP_N, mat, row_begin, row_end, nvec);
 }
 
 int spmv_multi_create_device_op(spmv_multi **m, int device, int op, IndexType nr_rows, IndexType nr_cols,
@@ -204,32 +194,8 @@ int spmv_multi_create_device_op(spmv_multi **m, int device, int op, IndexType nr
 {
     if (bad_op("spmv_multi_create_device_op", op))
         return 1;
-    if (op == SPMV_OP_N)
-        return spmv_multi_create_device(m, device, nr_rows, nr_cols, nr_nzeros, d_row_ptr, d_col_ind, d_values, nvec,
-                                        stream);
-    if (!m || (nr_rows && !d_row_ptr)) {
-        set_error("spmv_multi_create_device_op: null argument");
-        return 1;
-    }
-    *m = nullptr;
-    if (multi_bad_nvec("spmv_multi_create_device_op", nvec))
-        return 1;
-    hipStream_t s = (hipStream_t)stream;
-    SPMV_TRY(hipSetDevice(device));
-    std::vector<IndexType> rp(size_t(nr_rows) + 1, 0u);
-    if (nr_rows) {
-        SPMV_TRY(hipMemcpyAsync(rp.data(), d_row_ptr, rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
-        SPMV_TRY(hipStreamSynchronize(s));
-    }
-    const IndexType base = rp[0];
-    for (auto &e : rp)
-        e -= base;
-    if (rp[nr_rows] != nr_nzeros) {
-        set_error("spmv_multi_create_device_op: row_ptr[n]-row_ptr[0] != nr_nzeros");
-        return 1;
-    }
-    return multi_create_transposed(m, device, nr_rows, nr_cols, rp.data(), d_col_ind ? d_col_ind + base : nullptr,
-                                   d_values ? d_values + base : nullptr, true, nvec, s);
+    return create_device(op == SPMV_OP_N ? "spmv_multi_create_device" : "spmv_multi_create_device_op", m, device, op,
+                         nr_rows, nr_cols, nr_nzeros, d_row_ptr, d_col_ind, d_values, nvec, stream);
 }
 
 int spmv_multi_create_host_op(spmv_multi **m, int device, int op, const csr_matrix *mat, IndexType row_begin,
@@ -237,22 +203,8 @@ int spmv_multi_create_host_op(spmv_multi **m, int device, int op, const csr_matr
 {
     if (bad_op("spmv_multi_create_host_op", op))
         return 1;
-    if (op == SPMV_OP_N)
-        return spmv_multi_create_host(m, device, mat, row_begin, row_end, nvec);
-    if (!m || !mat || row_begin > row_end || row_end > mat->nr_rows) {
-        set_error("spmv_multi_create_host_op: bad arguments");
-        return 1;
-    }
-    *m = nullptr;
-    if (multi_bad_nvec("spmv_multi_create_host_op", nvec))
-        return 1;
-    const IndexType n = row_end - row_begin;
-    const IndexType base = mat->row_ptr[row_begin];
-    std::vector<IndexType> rp(size_t(n) + 1);
-    for (IndexType r = 0; r <= n; ++r)
-        rp[r] = mat->row_ptr[row_begin + r] - base;
-    return multi_create_transposed(m, device, n, mat->nr_cols, rp.data(), mat->col_ind + base, mat->values + base,
-                                   false, nvec, nullptr);
+    return create_host(op == SPMV_OP_N ? "spmv_multi_create_host" : "spmv_multi_create_host_op", m, device, op, mat,
+                       row_begin, row_end, nvec);
 }
 
 int spmv_multi_run(const spmv_multi *m, const ValueType *d_X, ValueType *d_Y, void *stream)

@@ -69,6 +69,47 @@ int upload_staged(void *dst, const void *src, size_t bytes, hipStream_t s)
     return 0;
 }
 
+int slice_from_device(const char *who, csr_slice &out, const void *handle, int device, IndexType n, IndexType m,
+                      IndexType nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col, const ValueType *d_val,
+                      hipStream_t stream)
+{
+    if (slice_device_args(who, handle, n, d_row_ptr))
+        return 1;
+    SPMV_TRY(hipSetDevice(device));
+    out.n = n;
+    out.m = m;
+    out.rp.assign(size_t(n) + 1, 0u);
+    if (n) {
+        SPMV_TRY(hipMemcpyAsync(out.rp.data(), d_row_ptr, out.rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost,
+                                stream));
+        SPMV_TRY(hipStreamSynchronize(stream));
+    }
+    out.col = d_col;
+    out.val = d_val;
+    out.on_device = true;
+    out.stream = stream;
+    return slice_rebase(who, out, &nr_nzeros);
+}
+
+int slice_entries_on_device(const csr_slice &sl, device_scratch &up_col, device_scratch &up_val,
+                            const IndexType **d_col, const ValueType **d_val)
+{
+    *d_col = sl.col;
+    *d_val = sl.val;
+    const uint64_t nnz = sl.nnz();
+    if (sl.on_device || !nnz)
+        return 0;
+    hipStream_t s = (hipStream_t)sl.stream;
+    SPMV_TRY(hipMalloc(&up_col.p, nnz * sizeof(IndexType)));
+    SPMV_TRY(hipMalloc(&up_val.p, nnz * sizeof(ValueType)));
+    if (upload_staged(up_col.p, sl.col, nnz * sizeof(IndexType), s) ||
+        upload_staged(up_val.p, sl.val, nnz * sizeof(ValueType), s))
+        return 1;
+    *d_col = (const IndexType *)up_col.p;
+    *d_val = (const ValueType *)up_val.p;
+    return 0;
+}
+
 // env SPMV_HW_TRACE=1: phase times of plan construction on stderr
 struct PhaseTrace {
     const bool on = std::getenv("SPMV_HW_TRACE") != nullptr;
@@ -477,25 +518,25 @@ static int time_layout(spmv_plan &P, const ValueType *d_x, ValueType *d_y, hipSt
     return 0;
 }
 
-int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows, IndexType nr_cols,
-                                 const IndexType *h_row_ptr, const IndexType *col_src,
-                                 const ValueType *val_src, bool src_on_device, hipStream_t s, int force_kernel)
+int plan_create_from_slice(spmv_plan **out, int device, int op, const csr_slice &sl, int force_kernel)
 {
     *out = nullptr;
-    PhaseTrace trace;
-    if (nr_rows > 0 && h_row_ptr[0] != 0) {
-        set_error("row_ptr must be rebased to 0");
-        return 1;
-    }
-    const uint64_t nnz = nr_rows ? h_row_ptr[nr_rows] : 0;
-    uint64_t nzr = 0;
-    for (IndexType r = 0; r < nr_rows; ++r) {
-        if (h_row_ptr[r + 1] < h_row_ptr[r]) {
-            set_error("row_ptr is not non-decreasing at row " + std::to_string(r));
+    if (op == SPMV_OP_T) {  // the slice's transpose (transpose.hip) through the same construction, n x m -> m x n
+        SPMV_TRY(hipSetDevice(device));
+        transposed_csr t;
+        if (transpose_slice(t, sl) || plan_create_from_slice(out, device, SPMV_OP_N, t.slice, force_kernel))
             return 1;
-        }
-        nzr += h_row_ptr[r + 1] > h_row_ptr[r];
+        (*out)->op = SPMV_OP_T;
+        return 0;
     }
+    PhaseTrace trace;
+    const IndexType nr_rows = sl.n, nr_cols = sl.m;
+    const IndexType *h_row_ptr = sl.rp.data();
+    hipStream_t s = (hipStream_t)sl.stream;
+    const uint64_t nnz = sl.nnz();
+    uint64_t nzr = 0;
+    for (IndexType r = 0; r < nr_rows; ++r)
+        nzr += h_row_ptr[r + 1] > h_row_ptr[r];
     if (nnz > 0 && nr_cols == 0) {
         set_error("matrix has non-zeros but zero columns");
         return 1;
@@ -511,21 +552,11 @@ int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows,
     p->has_empty = nzr < nr_rows;
 
     // device copies of the CSR entries (host path: upload), validated before any kernel gathers
-    struct Tmp {
-        void *p = nullptr;
-        ~Tmp() { if (p) (void)hipFree(p); }
-    } tcol, tval, trp, tbad;
-    const IndexType *d_col = col_src;
-    const ValueType *d_val = val_src;
-    if (!src_on_device && nnz) {
-        SPMV_TRY(hipMalloc(&tcol.p, nnz * sizeof(IndexType)));
-        SPMV_TRY(hipMalloc(&tval.p, nnz * sizeof(ValueType)));
-        if (upload_staged(tcol.p, col_src, nnz * sizeof(IndexType), s) ||
-            upload_staged(tval.p, val_src, nnz * sizeof(ValueType), s))
-            return 1;
-        d_col = (const IndexType *)tcol.p;
-        d_val = (const ValueType *)tval.p;
-    }
+    device_scratch tcol, tval, trp, tbad;
+    const IndexType *d_col = nullptr;
+    const ValueType *d_val = nullptr;
+    if (slice_entries_on_device(sl, tcol, tval, &d_col, &d_val))
+        return 1;
     trace("row_ptr scan + upload", s);
     if (nnz) {
         SPMV_TRY(hipMalloc(&tbad.p, sizeof(uint32_t)));
@@ -609,7 +640,7 @@ int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows,
         const char *det = std::getenv("SPMV_SWEEP_DETERMINISTIC");
         const bool fixed_bits = det && det[0] == '1';
         constexpr double kTuneBand = 0.97;
-        Tmp tx, ty;
+        device_scratch tx, ty;
         SPMV_TRY(hipMalloc(&tx.p, std::max<size_t>(nr_cols, 1) * sizeof(ValueType)));
         SPMV_TRY(hipMalloc(&ty.p, std::max<size_t>(nr_rows, 1) * sizeof(ValueType)));
         SPMV_TRY(hipMemsetAsync(tx.p, 0, std::max<size_t>(nr_cols, 1) * sizeof(ValueType), s));
@@ -771,66 +802,42 @@ uint64_t spmv_plan::algorithmic_bytes() const
            uint64_t(nr_cols) * sizeof(ValueType) + uint64_t(nr_rows) * sizeof(ValueType);
 }
 
+// The four plan creates: `who` names the caller in the messages (op = SPMV_OP_N through an _op
+// function is the function without an op, and reports as it)
+static int create_device(const char *who, spmv_plan **plan, int device, int op, IndexType nr_rows, IndexType nr_cols,
+                         IndexType nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col_ind,
+                         const ValueType *d_values, void *stream)
+{
+    csr_slice sl;
+    if (slice_from_device(who, sl, plan, device, nr_rows, nr_cols, nr_nzeros, d_row_ptr, d_col_ind, d_values,
+                          (hipStream_t)stream))
+        return 1;
+    return plan_create_from_slice(plan, device, op, sl);
+}
+
+static int create_host(const char *who, spmv_plan **plan, int device, int op, const csr_matrix *m, IndexType row_begin,
+                       IndexType row_end)
+{
+    csr_slice sl;
+    if (slice_from_host(who, sl, plan, m, row_begin, row_end))
+        return 1;
+    return plan_create_from_slice(plan, device, op, sl);
+}
+
 extern "C" {
 
 int spmv_plan_create_device(spmv_plan **plan, int device, IndexType nr_rows, IndexType nr_cols,
                             IndexType nr_nzeros, const IndexType *d_row_ptr,
                             const IndexType *d_col_ind, const ValueType *d_values, void *stream)
 {
-    if (!plan || (nr_rows && !d_row_ptr)) {
-        set_error("spmv_plan_create_device: null argument");
-        return 1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    SPMV_TRY(hipSetDevice(device));
-    std::vector<IndexType> rp(size_t(nr_rows) + 1, 0u);
-    if (nr_rows) {
-        SPMV_TRY(hipMemcpyAsync(rp.data(), d_row_ptr, rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
-        SPMV_TRY(hipStreamSynchronize(s));
-    }
-    const IndexType base = rp[0];
-    for (auto &e : rp)
-        e -= base;
-    if (rp[nr_rows] != nr_nzeros) {
-        set_error("spmv_plan_create_device: row_ptr[n]-row_ptr[0] != nr_nzeros");
-        return 1;
-    }
-    return plan_create_from_host_rowptr(plan, device, nr_rows, nr_cols, rp.data(),
-                                        d_col_ind ? d_col_ind + base : nullptr,
-                                        d_values ? d_values + base : nullptr, true, s);
+    return create_device("spmv_plan_create_device", plan, device, SPMV_OP_N, nr_rows, nr_cols, nr_nzeros, d_row_ptr,
+                         d_col_ind, d_values, stream);
 }
 
 int spmv_plan_create_host(spmv_plan **plan, int device, const csr_matrix *m, IndexType row_begin,
                           IndexType row_end)
 {
-    if (!plan || !m || row_begin > row_end || row_end > m->nr_rows) {
-        set_error("spmv_plan_create_host: bad arguments");
-        return 1;
-    }
-    const IndexType n = row_end - row_begin;
-    const IndexType base = m->row_ptr[row_begin];
-    std::vector<IndexType> rp(size_t(n) + 1);
-    for (IndexType r = 0; r <= n; ++r)
-        rp[r] = m->row_ptr[row_begin + r] - base;
-    hipStream_t s = nullptr;
-    return plan_create_from_host_rowptr(plan, device, n, m->nr_cols, rp.data(), m->col_ind + base,
-                                        m->values + base, false, s);
-}
-
-// op = T: the slice's transpose (transpose.hip) through the same plan construction, n x m -> m x n
-static int plan_create_transposed(spmv_plan **plan, int device, IndexType n, IndexType m, const IndexType *h_rp,
-                                  const IndexType *col_src, const ValueType *val_src, bool src_on_device,
-                                  hipStream_t s)
-{
-    *plan = nullptr;
-    SPMV_TRY(hipSetDevice(device));
-    transposed_csr t;
-    if (transpose_slice(t, n, m, h_rp, col_src, val_src, src_on_device, s))
-        return 1;
-    if (plan_create_from_host_rowptr(plan, device, m, n, t.rp.data(), t.d_col, t.d_val, true, s))
-        return 1;
-    (*plan)->op = SPMV_OP_T;
-    return 0;
+    return create_host("spmv_plan_create_host", plan, device, SPMV_OP_N, m, row_begin, row_end);
 }
 
 int spmv_plan_create_device_op(spmv_plan **plan, int device, int op, IndexType nr_rows, IndexType nr_cols,
@@ -839,29 +846,8 @@ int spmv_plan_create_device_op(spmv_plan **plan, int device, int op, IndexType n
 {
     if (bad_op("spmv_plan_create_device_op", op))
         return 1;
-    if (op == SPMV_OP_N)
-        return spmv_plan_create_device(plan, device, nr_rows, nr_cols, nr_nzeros, d_row_ptr, d_col_ind, d_values,
-                                       stream);
-    if (!plan || (nr_rows && !d_row_ptr)) {
-        set_error("spmv_plan_create_device_op: null argument");
-        return 1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    SPMV_TRY(hipSetDevice(device));
-    std::vector<IndexType> rp(size_t(nr_rows) + 1, 0u);
-    if (nr_rows) {
-        SPMV_TRY(hipMemcpyAsync(rp.data(), d_row_ptr, rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
-        SPMV_TRY(hipStreamSynchronize(s));
-    }
-    const IndexType base = rp[0];
-    for (auto &e : rp)
-        e -= base;
-    if (rp[nr_rows] != nr_nzeros) {
-        set_error("spmv_plan_create_device_op: row_ptr[n]-row_ptr[0] != nr_nzeros");
-        return 1;
-    }
-    return plan_create_transposed(plan, device, nr_rows, nr_cols, rp.data(), d_col_ind ? d_col_ind + base : nullptr,
-                                  d_values ? d_values + base : nullptr, true, s);
+    return create_device(op == SPMV_OP_N ? "spmv_plan_create_device" : "spmv_plan_create_device_op", plan, device, op,
+                         nr_rows, nr_cols, nr_nzeros, d_row_ptr, d_col_ind, d_values, stream);
 }
 
 int spmv_plan_create_host_op(spmv_plan **plan, int device, int op, const csr_matrix *m, IndexType row_begin,
@@ -869,19 +855,8 @@ int spmv_plan_create_host_op(spmv_plan **plan, int device, int op, const csr_mat
 {
     if (bad_op("spmv_plan_create_host_op", op))
         return 1;
-    if (op == SPMV_OP_N)
-        return spmv_plan_create_host(plan, device, m, row_begin, row_end);
-    if (!plan || !m || row_begin > row_end || row_end > m->nr_rows) {
-        set_error("spmv_plan_create_host_op: bad arguments");
-        return 1;
-    }
-    const IndexType n = row_end - row_begin;
-    const IndexType base = m->row_ptr[row_begin];
-    std::vector<IndexType> rp(size_t(n) + 1);
-    for (IndexType r = 0; r <= n; ++r)
-        rp[r] = m->row_ptr[row_begin + r] - base;
-    return plan_create_transposed(plan, device, n, m->nr_cols, rp.data(), m->col_ind + base, m->values + base, false,
-                                  nullptr);
+    return create_host(op == SPMV_OP_N ? "spmv_plan_create_host" : "spmv_plan_create_host_op", plan, device, op, m,
+                       row_begin, row_end);
 }
 
 int spmv_plan_get_op(const spmv_plan *plan, int *op)

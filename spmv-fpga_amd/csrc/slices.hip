@@ -605,36 +605,33 @@ int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
     p.nslices = S;
     p.slice_slots = slots;
     const uint64_t E = slots * kWave;
-    struct Tmp {
-        void *q = nullptr;
-        ~Tmp() { if (q) (void)hipFree(q); }
-    } tcol, tspan, trp;
+    device_scratch tcol, tspan, trp;
     SPMV_TRY(hipMalloc((void **)&p.d_slot_off, (S + 1) * 4));
     SPMV_TRY(hipMalloc((void **)&p.d_slice_len, std::max<size_t>(n, 1) * 4));
     SPMV_TRY(hipMalloc((void **)&p.d_val, std::max<uint64_t>(E, 2) * sizeof(ValueType)));
     SPMV_TRY(hipMalloc((void **)&p.d_sbase, std::max<uint64_t>(slots, 1) * 4));
-    SPMV_TRY(hipMalloc(&tcol.q, std::max<uint64_t>(E, 2) * 4));
-    SPMV_TRY(hipMalloc(&tspan.q, 4));
-    SPMV_TRY(hipMalloc(&trp.q, (size_t(n) + 1) * 4));
+    SPMV_TRY(hipMalloc(&tcol.p, std::max<uint64_t>(E, 2) * 4));
+    SPMV_TRY(hipMalloc(&tspan.p, 4));
+    SPMV_TRY(hipMalloc(&trp.p, (size_t(n) + 1) * 4));
     SPMV_TRY(hipMemcpyAsync(p.d_slot_off, so.data(), (S + 1) * 4, hipMemcpyHostToDevice, s));
     if (n)
         SPMV_TRY(hipMemcpyAsync(p.d_slice_len, len.data(), size_t(n) * 4, hipMemcpyHostToDevice, s));
-    SPMV_TRY(hipMemcpyAsync(trp.q, h_rp, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
-    SPMV_TRY(hipMemsetAsync(tspan.q, 0, 4, s));
+    SPMV_TRY(hipMemcpyAsync(trp.p, h_rp, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
+    SPMV_TRY(hipMemsetAsync(tspan.p, 0, 4, s));
     uint32_t span = 0;
     if (n) {
-        hipLaunchKernelGGL(k_slices_fill, dim3((n + 255) / 256), dim3(256), 0, s, (const IndexType *)trp.q, d_col_src,
-                           d_val_src, n, p.d_slot_off, p.d_val, (uint32_t *)tcol.q);
+        hipLaunchKernelGGL(k_slices_fill, dim3((n + 255) / 256), dim3(256), 0, s, (const IndexType *)trp.p, d_col_src,
+                           d_val_src, n, p.d_slot_off, p.d_val, (uint32_t *)tcol.p);
         SPMV_TRY(hipGetLastError());
         const uint32_t rest = (uint32_t)(S * kWave - n);
         if (rest)
             hipLaunchKernelGGL(k_slices_tail, dim3((rest + 63) / 64), dim3(64), 0, s, n, (uint32_t)S, p.d_slot_off,
-                               p.d_val, (uint32_t *)tcol.q);
+                               p.d_val, (uint32_t *)tcol.p);
         SPMV_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_slices_base, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off, (uint32_t)S,
-                           (const uint32_t *)tcol.q, p.d_sbase, (uint32_t *)tspan.q);
+                           (const uint32_t *)tcol.p, p.d_sbase, (uint32_t *)tspan.p);
         SPMV_TRY(hipGetLastError());
-        SPMV_TRY(hipMemcpyAsync(&span, tspan.q, 4, hipMemcpyDeviceToHost, s));
+        SPMV_TRY(hipMemcpyAsync(&span, tspan.p, 4, hipMemcpyDeviceToHost, s));
         SPMV_TRY(hipStreamSynchronize(s));
     }
     // env SPMV_SLICE_ACC=32 (fp32 library): fp32 row accumulator, bitwise spmv_gold in fp32
@@ -649,12 +646,12 @@ int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
     if (ob == 4 && narrow && n) {  // try up to 4 clusters of 16384 columns per slot
         uint32_t *sb4 = nullptr, bad = 1;
         SPMV_TRY(hipMalloc((void **)&sb4, std::max<uint64_t>(slots, 1) * 16));
-        SPMV_TRY(hipMemsetAsync(tspan.q, 0, 4, s));
+        SPMV_TRY(hipMemsetAsync(tspan.p, 0, 4, s));
         hipLaunchKernelGGL(k_slices_clusters, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off,
-                           (uint32_t)S, (const uint32_t *)tcol.q, sb4, (uint32_t *)tspan.q);
+                           (uint32_t)S, (const uint32_t *)tcol.p, sb4, (uint32_t *)tspan.p);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess)
-            e = hipMemcpyAsync(&bad, tspan.q, 4, hipMemcpyDeviceToHost, s);
+            e = hipMemcpyAsync(&bad, tspan.p, 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess)
             e = hipStreamSynchronize(s);
         if (e != hipSuccess || bad) {
@@ -665,7 +662,7 @@ int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
             p.d_sbase = sb4;
             SPMV_TRY(hipMalloc(&p.d_colnar, std::max<uint64_t>(E, 2) * 2));
             hipLaunchKernelGGL(k_slices_off_cl, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off,
-                               (uint32_t)S, (const uint32_t *)tcol.q, (const uint32_t *)p.d_sbase,
+                               (uint32_t)S, (const uint32_t *)tcol.p, (const uint32_t *)p.d_sbase,
                                (uint16_t *)p.d_colnar);
             SPMV_TRY(hipGetLastError());
             SPMV_TRY(hipStreamSynchronize(s));
@@ -677,21 +674,21 @@ int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
     p.slice_off_bytes = ob;
     if (ob == 4) {  // absolute columns: padding lanes get column 0 (masked), bases 0
         if (E) {
-            hipLaunchKernelGGL(k_slices_abs, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, (uint32_t *)tcol.q, E);
+            hipLaunchKernelGGL(k_slices_abs, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, (uint32_t *)tcol.p, E);
             SPMV_TRY(hipGetLastError());
         }
         SPMV_TRY(hipMemsetAsync(p.d_sbase, 0, std::max<uint64_t>(slots, 1) * 4, s));
-        p.d_colnar = tcol.q;
-        tcol.q = nullptr;
+        p.d_colnar = tcol.p;
+        tcol.p = nullptr;
     } else {
         SPMV_TRY(hipMalloc(&p.d_colnar, std::max<uint64_t>(E, 2) * ob));
         if (n) {
             if (ob == 1)
                 hipLaunchKernelGGL(k_slices_off<uint8_t>, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off,
-                                   (uint32_t)S, (const uint32_t *)tcol.q, p.d_sbase, (uint8_t *)p.d_colnar);
+                                   (uint32_t)S, (const uint32_t *)tcol.p, p.d_sbase, (uint8_t *)p.d_colnar);
             else
                 hipLaunchKernelGGL(k_slices_off<uint16_t>, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off,
-                                   (uint32_t)S, (const uint32_t *)tcol.q, p.d_sbase, (uint16_t *)p.d_colnar);
+                                   (uint32_t)S, (const uint32_t *)tcol.p, p.d_sbase, (uint16_t *)p.d_colnar);
             SPMV_TRY(hipGetLastError());
         }
     }

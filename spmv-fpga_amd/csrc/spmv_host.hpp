@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "csr_hw_wrapper.h"
 
@@ -27,6 +28,32 @@ inline const char *ablation_env(const char *name)
     return nullptr;
 #endif
 }
+
+// The rows [row_begin, row_end) of a CSR matrix as every create call takes them:
+// filled by slice_from_host, or from device arrays by slice_from_device (spmv_internal.hpp), and
+// consumed by plan_create_from_slice, multi_create and transpose_slice.
+struct csr_slice {
+    IndexType n = 0, m = 0;           // rows of the slice, columns of the matrix
+    std::vector<IndexType> rp;        // n + 1 on the host, rp[0] = 0, non-decreasing
+    const IndexType *col = nullptr;   // the slice's entries: the caller's arrays offset by the
+    const ValueType *val = nullptr;   // slice's first entry (null stays null)
+    bool on_device = false;           // where col / val live
+    void *stream = nullptr;           // opaque here (a hipStream_t): the stream the creates work on
+    uint64_t nnz() const { return rp.empty() ? 0 : rp.back(); }
+};
+
+// Fills `out` with rows [row_begin, row_end) of a host matrix. `handle` is the caller's
+// out-handle: null is a bad argument like a null matrix or a range outside it
+// ("<who>: bad arguments").
+int slice_from_host(const char *who, csr_slice &out, const void *handle, const csr_matrix *m, IndexType row_begin,
+                    IndexType row_end);
+// The null check of a device slice ("<who>: null argument"): the out-handle, and row_ptr unless
+// there are no rows. slice_from_device makes it before its first HIP call.
+int slice_device_args(const char *who, const void *handle, IndexType n, const IndexType *d_row_ptr);
+// The fillers' common end. s.rp holds n + 1 row_ptr entries as the caller has them and s.col /
+// s.val the caller's arrays: subtracts rp[0], checks rp[n] against *nr_nzeros when given (the
+// message names <who>), offsets col / val and checks that rp does not decrease.
+int slice_rebase(const char *who, csr_slice &s, const IndexType *nr_nzeros = nullptr);
 
 // wall clock in microseconds (util.cpp:3-8)
 double timestamp_us();

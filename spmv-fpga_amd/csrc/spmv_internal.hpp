@@ -307,13 +307,30 @@ int sweep_materialize_rc(spmv_plan &p);  // delta plan: rebuild the 12-byte rc w
 // workgroups can flag each panel's y as it is stored (spmv_plan::y_flag)
 bool sweep_can_flag_panels(const spmv_plan &p);
 
+// device scratch of a build step, freed on scope exit
+struct device_scratch {
+    void *p = nullptr;
+    ~device_scratch()
+    {
+        if (p)
+            (void)hipFree(p);
+    }
+};
+
 // plan.cpp helpers shared with the wrapper
 int upload_staged(void *dst, const void *src, size_t bytes, hipStream_t s);  // pageable H2D, synchronous
-int plan_create_from_host_rowptr(spmv_plan **out, int device, IndexType nr_rows, IndexType nr_cols,
-                                 const IndexType *h_row_ptr /* rebased, nr_rows+1 */,
-                                 const IndexType *col_src, const ValueType *val_src,
-                                 bool src_on_device, hipStream_t s, int force_kernel = -1);
+// Fills `out` (spmv_host.hpp) from device arrays: slice_device_args, then hipSetDevice, row_ptr
+// copied to the host on `stream`, slice_rebase against nr_nzeros.
+int slice_from_device(const char *who, csr_slice &out, const void *handle, int device, IndexType n, IndexType m,
+                      IndexType nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col, const ValueType *d_val,
+                      hipStream_t stream);
+// The slice's entries on the device: its own pointers, or (host slice) copies uploaded into
+// up_col / up_val on the slice's stream
+int slice_entries_on_device(const csr_slice &sl, device_scratch &up_col, device_scratch &up_val,
+                            const IndexType **d_col, const ValueType **d_val);
+// The plan of the slice (op = SPMV_OP_T: of its device transpose, transpose_slice, the plan's op set).
 // force_kernel >= 0: that kernel as if env SPMV_HW_KERNEL named it (spmv_multi's native path)
+int plan_create_from_slice(spmv_plan **out, int device, int op, const csr_slice &sl, int force_kernel = -1);
 
 // transpose.hip
 bool bad_op(const char *who, int op);  // true (and the error set) unless op is SPMV_OP_N or SPMV_OP_T
@@ -325,16 +342,13 @@ int check_transpose_size(const char *who, uint64_t nnz);  // nonzero (error set)
 int csr_transpose_device(IndexType n, IndexType m, const IndexType *h_rp, const IndexType *d_col,
                          const ValueType *d_val, IndexType *d_t_rp, IndexType *d_t_col, ValueType *d_t_val,
                          hipStream_t s);
-// A^T of a slice as the create functions take it: row_ptr on the host, entries on the device
+// A^T of a slice as the creates take it: an m x n device slice whose entries live in the two buffers
 struct transposed_csr {
-    std::vector<IndexType> rp;  // m + 1, starts at 0
-    IndexType *d_col = nullptr;
-    ValueType *d_val = nullptr;
-    ~transposed_csr();
+    csr_slice slice;
+    device_scratch col, val;
 };
-// col_src / val_src on the host (uploaded first) or the device; checks h_rp and the size limit
-int transpose_slice(transposed_csr &t, IndexType n, IndexType m, const IndexType *h_rp, const IndexType *col_src,
-                    const ValueType *val_src, bool src_on_device, hipStream_t s);
+// sl's entries on the host (uploaded first) or the device; checks the size limit
+int transpose_slice(transposed_csr &t, const csr_slice &sl);
 
 // mgpu.cpp helpers for spmv_hw's RCCL merge (csr_hw_wrapper.cpp): a clique over n distinct
 // devices (one rank each, ncclCommInitAll) that borrows the units' plans and takes each device's

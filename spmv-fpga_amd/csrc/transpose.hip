@@ -79,15 +79,6 @@ __global__ void k_tr_gather(const uint32_t *__restrict__ idx, const uint32_t *__
     t_val[k] = val[e];
 }
 
-struct Tmp {
-    void *p = nullptr;
-    ~Tmp()
-    {
-        if (p)
-            (void)hipFree(p);
-    }
-};
-
 inline unsigned tr_blocks(uint64_t items) { return (unsigned)((items + kTrThreads - 1) / kTrThreads); }
 
 }  // namespace
@@ -124,7 +115,7 @@ int csr_transpose_device(IndexType n, IndexType m, const IndexType *h_rp, const 
         SPMV_TRY(hipStreamSynchronize(s));
         return 0;
     }
-    Tmp bad, rp, row, i0, i1, work;
+    device_scratch bad, rp, row, i0, i1, work;
     SPMV_TRY(hipMalloc(&bad.p, sizeof(uint32_t)));
     SPMV_TRY(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
     SPMV_TRY(launch_validate(d_col, nnz, m, (uint32_t *)bad.p, s));
@@ -166,44 +157,32 @@ int csr_transpose_device(IndexType n, IndexType m, const IndexType *h_rp, const 
     return 0;
 }
 
-transposed_csr::~transposed_csr()
+int transpose_slice(transposed_csr &t, const csr_slice &sl)
 {
-    if (d_col)
-        (void)hipFree(d_col);
-    if (d_val)
-        (void)hipFree(d_val);
-}
-
-int transpose_slice(transposed_csr &t, IndexType n, IndexType m, const IndexType *h_rp, const IndexType *col_src,
-                    const ValueType *val_src, bool src_on_device, hipStream_t s)
-{
-    const uint64_t nnz = n ? h_rp[n] : 0;
-    for (IndexType r = 0; r < n; ++r)
-        if (h_rp[r + 1] < h_rp[r]) {
-            set_error("row_ptr is not non-decreasing at row " + std::to_string(r));
-            return 1;
-        }
+    const IndexType n = sl.n, m = sl.m;
+    const uint64_t nnz = sl.nnz();
+    hipStream_t s = (hipStream_t)sl.stream;
     if (check_transpose_size("csr transpose", nnz))
         return 1;
-    Tmp up_col, up_val, t_rp;
-    const IndexType *d_col = col_src;
-    const ValueType *d_val = val_src;
-    if (!src_on_device && nnz) {
-        SPMV_TRY(hipMalloc(&up_col.p, nnz * sizeof(IndexType)));
-        SPMV_TRY(hipMalloc(&up_val.p, nnz * sizeof(ValueType)));
-        if (upload_staged(up_col.p, col_src, nnz * sizeof(IndexType), s) ||
-            upload_staged(up_val.p, val_src, nnz * sizeof(ValueType), s))
-            return 1;
-        d_col = (const IndexType *)up_col.p;
-        d_val = (const ValueType *)up_val.p;
-    }
-    SPMV_TRY(hipMalloc(&t_rp.p, (size_t(m) + 1) * sizeof(IndexType)));
-    SPMV_TRY(hipMalloc((void **)&t.d_col, std::max<uint64_t>(nnz, 1) * sizeof(IndexType)));
-    SPMV_TRY(hipMalloc((void **)&t.d_val, std::max<uint64_t>(nnz, 1) * sizeof(ValueType)));
-    if (csr_transpose_device(n, m, h_rp, d_col, d_val, (IndexType *)t_rp.p, t.d_col, t.d_val, s))
+    device_scratch up_col, up_val, t_rp;
+    const IndexType *d_col = nullptr;
+    const ValueType *d_val = nullptr;
+    if (slice_entries_on_device(sl, up_col, up_val, &d_col, &d_val))
         return 1;
-    t.rp.resize(size_t(m) + 1);
-    SPMV_TRY(hipMemcpyAsync(t.rp.data(), t_rp.p, t.rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
+    SPMV_TRY(hipMalloc(&t_rp.p, (size_t(m) + 1) * sizeof(IndexType)));
+    SPMV_TRY(hipMalloc(&t.col.p, std::max<uint64_t>(nnz, 1) * sizeof(IndexType)));
+    SPMV_TRY(hipMalloc(&t.val.p, std::max<uint64_t>(nnz, 1) * sizeof(ValueType)));
+    if (csr_transpose_device(n, m, sl.rp.data(), d_col, d_val, (IndexType *)t_rp.p, (IndexType *)t.col.p,
+                             (ValueType *)t.val.p, s))
+        return 1;
+    t.slice.n = m;
+    t.slice.m = n;
+    t.slice.rp.resize(size_t(m) + 1);
+    t.slice.col = (const IndexType *)t.col.p;
+    t.slice.val = (const ValueType *)t.val.p;
+    t.slice.on_device = true;
+    t.slice.stream = sl.stream;
+    SPMV_TRY(hipMemcpyAsync(t.slice.rp.data(), t_rp.p, t.slice.rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
     SPMV_TRY(hipStreamSynchronize(s));
     return 0;
 }
@@ -217,31 +196,11 @@ extern "C" int spmv_csr_transpose_device(int device, IndexType nr_rows, IndexTyp
                                          const ValueType *d_values, IndexType *d_t_row_ptr, IndexType *d_t_col_ind,
                                          ValueType *d_t_values, void *stream)
 {
-    if (!d_t_row_ptr || (nr_rows && !d_row_ptr)) {
-        set_error("spmv_csr_transpose_device: null argument");
+    csr_slice sl;  // d_t_row_ptr stands where the creates have their out-handle: null is a null argument
+    if (slice_from_device("spmv_csr_transpose_device", sl, d_t_row_ptr, device, nr_rows, nr_cols, nr_nzeros, d_row_ptr,
+                          d_col_ind, d_values, (hipStream_t)stream) ||
+        check_transpose_size("spmv_csr_transpose_device", nr_nzeros))
         return 1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    SPMV_TRY(hipSetDevice(device));
-    std::vector<IndexType> rp(size_t(nr_rows) + 1, 0u);
-    if (nr_rows) {
-        SPMV_TRY(hipMemcpyAsync(rp.data(), d_row_ptr, rp.size() * sizeof(IndexType), hipMemcpyDeviceToHost, s));
-        SPMV_TRY(hipStreamSynchronize(s));
-    }
-    const IndexType base = rp[0];
-    for (auto &e : rp)
-        e -= base;
-    if (rp[nr_rows] != nr_nzeros) {
-        set_error("spmv_csr_transpose_device: row_ptr[n]-row_ptr[0] != nr_nzeros");
-        return 1;
-    }
-    if (check_transpose_size("spmv_csr_transpose_device", nr_nzeros))
-        return 1;
-    for (IndexType r = 0; r < nr_rows; ++r)
-        if (rp[r + 1] < rp[r]) {
-            set_error("row_ptr is not non-decreasing at row " + std::to_string(r));
-            return 1;
-        }
-    return csr_transpose_device(nr_rows, nr_cols, rp.data(), d_col_ind ? d_col_ind + base : nullptr,
-                                d_values ? d_values + base : nullptr, d_t_row_ptr, d_t_col_ind, d_t_values, s);
+    return csr_transpose_device(sl.n, sl.m, sl.rp.data(), sl.col, sl.val, d_t_row_ptr, d_t_col_ind, d_t_values,
+                                (hipStream_t)stream);
 }

@@ -394,25 +394,16 @@ class Plan:
         h = ctypes.c_void_p()
         n = row_ptr.numel() - 1
         nnz = int(row_ptr[-1].item()) - int(row_ptr[0].item()) if n >= 0 else 0
-        if transpose:
-            lib._ok(lib.L.spmv_plan_create_device_op(ctypes.byref(h), device, OP_T, n, nr_cols, nnz & 0xFFFFFFFF,
-                                                     row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(),
-                                                     _stream_ptr(stream)), "spmv_plan_create_device_op")
-            return cls(lib, h)
-        lib._ok(lib.L.spmv_plan_create_device(ctypes.byref(h), device, n, nr_cols, nnz & 0xFFFFFFFF,
-                                              row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(),
-                                              _stream_ptr(stream)), "spmv_plan_create_device")
+        name, op = ("spmv_plan_create_device_op", (OP_T,)) if transpose else ("spmv_plan_create_device", ())
+        lib._ok(getattr(lib.L, name)(ctypes.byref(h), device, *op, n, nr_cols, nnz & 0xFFFFFFFF, row_ptr.data_ptr(),
+                                     col.data_ptr(), val.data_ptr(), _stream_ptr(stream)), name)
         return cls(lib, h)
 
     @classmethod
     def from_host(cls, lib: Lib, matrix, row_begin: int, row_end: int, device: int = 0, transpose: bool = False):
         h = ctypes.c_void_p()
-        if transpose:
-            lib._ok(lib.L.spmv_plan_create_host_op(ctypes.byref(h), device, OP_T, ctypes.byref(matrix), row_begin,
-                                                   row_end), "spmv_plan_create_host_op")
-            return cls(lib, h)
-        lib._ok(lib.L.spmv_plan_create_host(ctypes.byref(h), device, ctypes.byref(matrix), row_begin, row_end),
-                "spmv_plan_create_host")
+        name, op = ("spmv_plan_create_host_op", (OP_T,)) if transpose else ("spmv_plan_create_host", ())
+        lib._ok(getattr(lib.L, name)(ctypes.byref(h), device, *op, ctypes.byref(matrix), row_begin, row_end), name)
         return cls(lib, h)
 
     @property
@@ -478,27 +469,20 @@ class MultiPlan:
         h = ctypes.c_void_p()
         n = row_ptr.numel() - 1
         nnz = int(row_ptr[-1].item()) - int(row_ptr[0].item()) if n >= 0 else 0
-        if transpose:
-            lib._ok(lib.L.spmv_multi_create_device_op(ctypes.byref(h), device, OP_T, n, nr_cols, nnz & 0xFFFFFFFF,
-                                                      row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), int(nvec),
-                                                      _stream_ptr(stream)), "spmv_multi_create_device_op")
-            return cls(lib, h, nr_cols, n, nvec, OP_T)
-        lib._ok(lib.L.spmv_multi_create_device(ctypes.byref(h), device, n, nr_cols, nnz & 0xFFFFFFFF,
-                                               row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), int(nvec),
-                                               _stream_ptr(stream)), "spmv_multi_create_device")
-        return cls(lib, h, n, nr_cols, nvec)
+        name, op = ("spmv_multi_create_device_op", (OP_T,)) if transpose else ("spmv_multi_create_device", ())
+        lib._ok(getattr(lib.L, name)(ctypes.byref(h), device, *op, n, nr_cols, nnz & 0xFFFFFFFF, row_ptr.data_ptr(),
+                                     col.data_ptr(), val.data_ptr(), int(nvec), _stream_ptr(stream)), name)
+        return cls(lib, h, nr_cols, n, nvec, OP_T) if transpose else cls(lib, h, n, nr_cols, nvec)
 
     @classmethod
     def from_host(cls, lib: Lib, matrix, row_begin: int, row_end: int, nvec: int, device: int = 0,
                   transpose: bool = False):
         h = ctypes.c_void_p()
-        if transpose:
-            lib._ok(lib.L.spmv_multi_create_host_op(ctypes.byref(h), device, OP_T, ctypes.byref(matrix), row_begin,
-                                                    row_end, int(nvec)), "spmv_multi_create_host_op")
-            return cls(lib, h, int(matrix.nr_cols), row_end - row_begin, nvec, OP_T)
-        lib._ok(lib.L.spmv_multi_create_host(ctypes.byref(h), device, ctypes.byref(matrix), row_begin, row_end,
-                                             int(nvec)), "spmv_multi_create_host")
-        return cls(lib, h, row_end - row_begin, int(matrix.nr_cols), nvec)
+        name, op = ("spmv_multi_create_host_op", (OP_T,)) if transpose else ("spmv_multi_create_host", ())
+        lib._ok(getattr(lib.L, name)(ctypes.byref(h), device, *op, ctypes.byref(matrix), row_begin, row_end,
+                                     int(nvec)), name)
+        n, m = row_end - row_begin, int(matrix.nr_cols)
+        return cls(lib, h, m, n, nvec, OP_T) if transpose else cls(lib, h, n, m, nvec)
 
     def run(self, X, Y, stream=None) -> None:
         for name, t, n in (("X", X, self.nr_cols), ("Y", Y, self.nr_rows)):

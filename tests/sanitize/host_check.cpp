@@ -6,6 +6,7 @@
 //   host_check read <file.mtx> <out.bin>   spmv_read_csr -> binary dump (n, m, nnz, row_ptr, col, val)
 //                                          and the header/matrix pair of calls, compared
 //   host_check partition                   random row_ptr, 1..16 units, against a restated S1 rule
+//   host_check slice                       slice_from_host on whole, empty, last-row and random ranges
 //   host_check schedule                    every exchange at 1..8 ranks, rows covered once
 //   host_check accumulate                  producer threads land parts while 16 threads add them
 //   host_check verify                      verification / storage_overhead semantics
@@ -105,6 +106,131 @@ static int cmd_partition()
     CHECK(spmv_partition_rows(nullptr, 0, 1, one) == 1);
     CHECK(std::strlen(spmv_hw_last_error()) > 0);
     std::printf("OK partition\n");
+    return 0;
+}
+
+// slice_from_host on one range of a matrix whose arrays are allocated at their exact sizes (a read
+// past row_ptr[row_end] is a heap overflow), against the rebased row_ptr computed here
+static void check_slice(const IndexType *rp, const IndexType *col, const ValueType *val, IndexType nr_rows,
+                        IndexType nr_cols, IndexType b, IndexType e)
+{
+    csr_matrix m;
+    std::memset(&m, 0, sizeof(m));
+    m.row_ptr = const_cast<IndexType *>(rp);
+    m.col_ind = const_cast<IndexType *>(col);
+    m.values = const_cast<ValueType *>(val);
+    m.nr_rows = nr_rows;
+    m.nr_cols = nr_cols;
+    m.nr_nzeros = rp[nr_rows];
+    int handle = 0;
+    csr_slice s;
+    CHECK(slice_from_host("check", s, &handle, &m, b, e) == 0);
+    const IndexType n = e - b, base = rp[b];
+    CHECK(s.n == n && s.m == nr_cols && !s.on_device && s.stream == nullptr);
+    CHECK(s.rp.size() == size_t(n) + 1);
+    CHECK(s.rp[0] == 0 && s.rp[n] == rp[e] - rp[b] && s.nnz() == uint64_t(rp[e] - rp[b]));
+    for (IndexType r = 0; r <= n; ++r)
+        CHECK(s.rp[r] == rp[b + r] - base);
+    CHECK(s.col == col + base && s.val == val + base);
+}
+
+static int cmd_slice()
+{
+    std::mt19937_64 g(11);
+    for (int it = 0; it < 200; ++it) {
+        const IndexType n = 1 + IndexType(g() % 300), ncols = 1 + IndexType(g() % 200);
+        // exact-size heap arrays: no vector capacity behind the last element
+        IndexType *rp = new IndexType[size_t(n) + 1];
+        rp[0] = 0;
+        for (IndexType r = 0; r < n; ++r)
+            rp[r + 1] = rp[r] + (g() % 3 == 0 ? 0 : IndexType(g() % 9));  // a third of the rows empty
+        const IndexType nnz = rp[n];
+        IndexType *col = new IndexType[nnz];
+        ValueType *val = new ValueType[nnz];
+        for (IndexType k = 0; k < nnz; ++k) {
+            col[k] = IndexType(g() % ncols);
+            val[k] = ValueType(int(g() % 64)) / 8;
+        }
+        check_slice(rp, col, val, n, ncols, 0, n);      // the whole matrix
+        check_slice(rp, col, val, n, ncols, 0, 0);      // empty, at the front
+        check_slice(rp, col, val, n, ncols, n, n);      // empty, at row_ptr's last entry
+        check_slice(rp, col, val, n, ncols, n - 1, n);  // the last row alone
+        // a range that starts and ends on empty rows (when the matrix has two)
+        IndexType e0 = n, e1 = n;
+        for (IndexType r = 0; r < n; ++r)
+            if (rp[r + 1] == rp[r]) {
+                if (e0 == n)
+                    e0 = r;
+                e1 = r;
+            }
+        if (e0 < e1)
+            check_slice(rp, col, val, n, ncols, e0, e1 + 1);
+        for (int k = 0; k < 8; ++k) {
+            const IndexType b = IndexType(g() % (size_t(n) + 1)), e = b + IndexType(g() % (size_t(n) - b + 1));
+            check_slice(rp, col, val, n, ncols, b, e);
+        }
+        delete[] rp;
+        delete[] col;
+        delete[] val;
+    }
+    {
+        // every entry lies before row_begin: base == nnz, col / val one past their arrays' end
+        const IndexType rp[5] = {0, 3, 5, 5, 5};
+        IndexType *col = new IndexType[5]{0, 1, 2, 0, 1};
+        ValueType *val = new ValueType[5]{1, 2, 3, 4, 5};
+        check_slice(rp, col, val, 4, 3, 2, 4);
+        check_slice(rp, col, val, 4, 3, 4, 4);
+        // the argument errors
+        csr_matrix m;
+        std::memset(&m, 0, sizeof(m));
+        m.row_ptr = const_cast<IndexType *>(rp);
+        m.col_ind = col;
+        m.values = val;
+        m.nr_rows = 4;
+        m.nr_cols = 3;
+        m.nr_nzeros = 5;
+        int handle = 0;
+        csr_slice s;
+        CHECK(slice_from_host("who", s, &handle, nullptr, 0, 0) != 0);
+        CHECK(!std::strcmp(spmv_hw_last_error(), "who: bad arguments"));
+        set_error("");
+        CHECK(slice_from_host("who", s, &handle, &m, 3, 2) != 0);
+        CHECK(!std::strcmp(spmv_hw_last_error(), "who: bad arguments"));
+        set_error("");
+        CHECK(slice_from_host("who", s, &handle, &m, 0, 5) != 0);
+        CHECK(!std::strcmp(spmv_hw_last_error(), "who: bad arguments"));
+        set_error("");
+        CHECK(slice_from_host("who", s, nullptr, &m, 0, 4) != 0);  // no out-handle
+        CHECK(!std::strcmp(spmv_hw_last_error(), "who: bad arguments"));
+        // a row_ptr that decreases inside the range is refused, outside it not looked at
+        const IndexType dec[5] = {0, 3, 2, 4, 4};
+        m.row_ptr = const_cast<IndexType *>(dec);
+        m.nr_nzeros = 4;
+        CHECK(slice_from_host("who", s, &handle, &m, 0, 4) != 0);
+        CHECK(std::strstr(spmv_hw_last_error(), "row_ptr is not non-decreasing at row 1"));
+        CHECK(slice_from_host("who", s, &handle, &m, 2, 4) == 0 && s.nnz() == 2);
+        // the device slice's null check, as far as it runs without a device
+        CHECK(slice_device_args("who", nullptr, 0, nullptr) != 0);
+        CHECK(!std::strcmp(spmv_hw_last_error(), "who: null argument"));
+        CHECK(slice_device_args("who", &handle, 4, nullptr) != 0);
+        CHECK(slice_device_args("who", &handle, 0, nullptr) == 0);
+        CHECK(slice_device_args("who", &handle, 4, rp) == 0);
+        // the fillers' common end as slice_from_device uses it: nr_nzeros must match
+        const IndexType col12[12] = {};
+        csr_slice d;
+        d.n = 2;
+        d.rp = {7, 9, 12};
+        d.col = col12;
+        IndexType z = 5;
+        CHECK(slice_rebase("who", d, &z) == 0 && d.rp[0] == 0 && d.rp[2] == 5 && d.col == col12 + 7 && !d.val);
+        d.rp = {7, 9, 12};
+        z = 4;
+        CHECK(slice_rebase("who", d, &z) != 0);
+        CHECK(!std::strcmp(spmv_hw_last_error(), "who: row_ptr[n]-row_ptr[0] != nr_nzeros"));
+        delete[] col;
+        delete[] val;
+    }
+    std::printf("OK slice\n");
     return 0;
 }
 
@@ -265,12 +391,14 @@ int main(int argc, char **argv)
         return cmd_read(argv[2], argv[3]);
     if (argc >= 2 && !std::strcmp(argv[1], "partition"))
         return cmd_partition();
+    if (argc >= 2 && !std::strcmp(argv[1], "slice"))
+        return cmd_slice();
     if (argc >= 2 && !std::strcmp(argv[1], "schedule"))
         return cmd_schedule();
     if (argc >= 2 && !std::strcmp(argv[1], "accumulate"))
         return cmd_accumulate();
     if (argc >= 2 && !std::strcmp(argv[1], "verify"))
         return cmd_verify();
-    std::fprintf(stderr, "usage: host_check read <mtx> <out> | partition | schedule | accumulate | verify\n");
+    std::fprintf(stderr, "usage: host_check read <mtx> <out> | partition | slice | schedule | accumulate | verify\n");
     return 2;
 }
