@@ -70,7 +70,6 @@ constexpr int kBinT = 1024;  // one workgroup per CU (LDS-bound in both passes)
 constexpr int kBinU = 4;     // pass 1: 64-lane steps of loads in flight per wave
 constexpr int kBinD = 8;     // pass 2: steps in flight per wave
 constexpr int kBinStageLoads = 10;  // pass 1: 16-B x loads per thread staging a window
-constexpr uint64_t kBinAlign = 128;  // entries: window ranges and pass-1 units start at multiples
 constexpr double kBinXccBias = 0.0;  // pass-1 window bias by default on a 256-CU chip (build_binned)
 constexpr uint16_t kBinSent = 0xFFFF;  // column offset of a pad entry: its product is exactly +0
                                        // (W <= 40960, so no real offset takes this value)
@@ -583,99 +582,27 @@ hipError_t launch_binned(const spmv_plan &p, const ValueType *d_x, ValueType *d_
     return hipGetLastError();
 }
 
-// Host: windows (W columns, a whole number of rounds of workgroups where x allows), panels
-// (nnz-balanced, <= rmax rows, whole rounds), then keys + counts, padded segment offsets, the
-// pass-1 units, and the scatter. rc 2: the segment table would be too large (the caller may use
-// another kernel).
-int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, const ValueType *d_val_src,
-                 hipStream_t s)
+static const char kWho[] = "build_binned";
+
+// build temporaries that outlive one step
+struct bin_scratch {
+    device_buf<uint32_t> key, cnt;      // per entry: its segment; per segment: its entries
+    device_buf<uint16_t> rowp;          // per entry: row - panel base
+    // delta layout: entries sorted by (segment, row)
+    device_buf<uint64_t> k64s, soff;    // sorted keys; segment offsets in sorted order
+    device_buf<uint32_t> idxs, pads, pscan, esc;  // sorted entry indices, escapes per entry, their scan, per segment
+    device_buf<unsigned char> tmp;
+};
+
+// rc 2 (the automatic choice then takes the sweep) when a panel or one row holds too much of the
+// slice for pass 2's LDS adds
+static int bin_check_skew(const spmv_plan &p, const IndexType *h_rp, const std::vector<uint32_t> &prow)
 {
-    constexpr uint32_t PER = 16 / sizeof(ValueType);
-    const IndexType n = p.nr_rows;
-    const uint64_t nnz = p.nnz, ncols = p.nr_cols;
-    int cus = 256;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, p.device) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-    }
-    // windows: W <= what 160 KiB of LDS holds (and the u16 offsets), a multiple of PER
-    const uint64_t wmax = std::min<uint64_t>((kSweepLdsBytes - 256) / sizeof(ValueType) / PER * PER, 65536);
-    uint64_t nwin = 1, W = PER;
-    if (ncols) {
-        const uint64_t rounds = std::max<uint64_t>(1, (ncols + cus * wmax - 1) / (cus * wmax));
-        nwin = std::min<uint64_t>(cus * rounds, (ncols + PER - 1) / PER);
-        W = ((ncols + nwin - 1) / nwin + PER - 1) / PER * PER;
-        nwin = (ncols + W - 1) / W;
-    }
-    // Pass-1 XCC bias: unit u runs on XCC u % 8 (tools/xcc_map_probe.py), and on the boxes
-    // measured pass 1's one-window workgroups take 266 us on even XCCs against 280 us on odd ones
-    // (tools/wg_timeline.py --binned, profiles/r03bn_binned_timeline.jsonl). With one unit per
-    // window (nwin a whole number of rounds) even windows get W (1 + d) columns, odd ones
-    // W (1 - d): every pair still spans 2W, so a column's window stays closed-form
-    // (bin_win_of). Env SPMV_BIN_XCC_BIAS=d (0 = even widths); only on a whole 256-CU chip.
-    uint64_t W0 = W, W1 = W;
-    {
-        const char *xb = ablation_env("SPMV_BIN_XCC_BIAS");
-        double d = xb ? std::atof(xb) : (cus == 256 ? kBinXccBias : 0.0);
-        if (!(d > -0.25 && d < 0.25) || nwin < (uint64_t)cus || nwin % cus)
-            d = 0.0;
-        const uint64_t w0 = std::min<uint64_t>(wmax, (uint64_t(std::llround(W * (1.0 + d))) + PER / 2) / PER * PER);
-        if (d != 0.0 && w0 >= PER && w0 < 2 * W) {
-            W0 = w0;
-            W1 = 2 * W - w0;
-            if (W1 > wmax) {  // a negative bias past the LDS: even widths
-                W0 = W1 = W;
-            }
-            const uint64_t pw = W0 + W1, k = ncols / pw, rem = ncols - k * pw;
-            nwin = 2 * k + (rem == 0 ? 0 : rem <= W0 ? 1 : 2);
-        }
-    }
-    // panels: y of <= rmax rows in LDS (fp64), plus the scratch slot of the pad entries
-    const uint32_t rmax = (uint32_t)std::min<uint64_t>((kSweepLdsBytes - 256) / 8 - 1, 65534);
-    std::vector<uint32_t> prow;
-    // subdivide: as in build_sweep, a run of (nearly) empty rows longer than a panel that no
-    // nnz-balanced cut reaches ends a bounded search; the first P's cuts are then kept and any
-    // panel above rmax rows is split into panels of at most rmax rows
-    const uint64_t P_first = std::max<uint64_t>({1, (n + rmax - 1) / rmax, std::min<uint64_t>(cus, n)});
-    bool subdivide = false;
-    for (uint64_t P = P_first;; ++P) {
-        if (P > (uint64_t)cus && P % cus)
-            P = (P + cus - 1) / cus * cus;  // whole rounds of workgroups
-        P = std::min<uint64_t>(P, std::max<uint64_t>(n, 1));
-        prow.assign(1, 0);
-        bool ok = true;
-        IndexType r = 0;
-        for (uint64_t q = 1; q <= P && ok; ++q) {
-            const uint64_t target = nnz * q / P;
-            IndexType e = (q == P) ? n : (IndexType)(std::lower_bound(h_rp, h_rp + n + 1, (IndexType)target) - h_rp);
-            e = std::max(e, r);
-            if (e - r > rmax && subdivide)
-                for (; e - r > rmax; r += rmax)
-                    prow.push_back(r + rmax);
-            if (e - r > rmax)
-                ok = false;
-            prow.push_back(e);
-            r = e;
-        }
-        if (ok)
-            break;
-        if (P >= n || P > 8 * std::max<uint64_t>(P_first, (uint64_t)cus)) {
-            if (subdivide) {
-                set_error("build_binned: cannot form panels");
-                return 1;
-            }
-            subdivide = true;
-            P = P_first - 1;  // (++P)
-        }
-    }
     const uint32_t P = (uint32_t)(prow.size() - 1);
-    uint32_t rmax_used = 0;
+    const uint64_t nnz = p.nnz;
     uint64_t emax = 0;
-    for (uint32_t q = 0; q < P; ++q) {
-        rmax_used = std::max(rmax_used, prow[q + 1] - prow[q]);
+    for (uint32_t q = 0; q < P; ++q)
         emax = std::max<uint64_t>(emax, uint64_t(h_rp[prow[q + 1]]) - h_rp[prow[q]]);
-    }
     // A panel far above the mean holds long rows; pass 2 would add their products into one LDS
     // address each, serialised (2M rows of ~16 plus two rows of 2M entries, fp32: 2.60 ms here
     // against 0.42 ms for the sweep, which cuts such panels into pieces). The automatic choice
@@ -688,208 +615,218 @@ int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
     // its adds all land on one LDS address. The longest row is checked on its own.
     if (p.bin_row_limit > 0.0 && P > 0) {
         uint64_t lmax = 0;
-        for (IndexType r = 0; r < n; ++r)
+        for (IndexType r = 0; r < p.nr_rows; ++r)
             lmax = std::max<uint64_t>(lmax, uint64_t(h_rp[r + 1]) - h_rp[r]);
         if (double(lmax) > p.bin_row_limit * double(nnz) / P) {
             set_error("build_binned: a row holds " + std::to_string(lmax) + " entries (long row)");
             return 2;
         }
     }
-    const uint64_t nseg = nwin * P;
+    return 0;
+}
+
+// Build step 1: every entry's (window, panel) segment and row offset, and the entries per segment
+static int bin_count(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, hipStream_t s, bin_scratch &t,
+                     std::vector<uint32_t> &cnt)
+{
+    const IndexType n = p.nr_rows;
+    const uint64_t nnz = p.nnz, nseg = cnt.size();
+    SPMV_BUILD_TRY(t.cnt.alloc(std::max<uint64_t>(nseg, 1)));
+    SPMV_BUILD_TRY(hipMemsetAsync(t.cnt, 0, std::max<uint64_t>(nseg, 1) * 4, s));
+    if (!nnz)
+        return 0;
+    device_buf<IndexType> d_rp;
+    SPMV_BUILD_TRY(d_rp.alloc(size_t(n) + 1));
+    SPMV_BUILD_TRY(hipMemcpyAsync(d_rp, h_rp, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(t.key.alloc(nnz));
+    SPMV_BUILD_TRY(t.rowp.alloc(nnz));
+    SPMV_BUILD_TRY(launch_items(k_bin_keys, nnz, 256, s, d_rp.get(), n, d_col_src, nnz, p.d_panel_row,
+                                (uint32_t)p.npanels, p.b_W, p.b_W1, t.key.get(), t.rowp.get(), t.cnt.get()));
+    SPMV_BUILD_TRY(hipMemcpyAsync(cnt.data(), t.cnt, nseg * 4, hipMemcpyDeviceToHost, s));
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Build step 2, the delta layout's front half: the entries sorted by (segment, row), the escape
+// entries each segment needs (esc) and -- when the layout is taken (*delta: `always`, or escapes
+// under 1 % of nnz) -- the scan and offsets its scatter reads. Otherwise its scratch is freed.
+static int bin_sort_rows(spmv_plan &p, hipStream_t s, bool always, const std::vector<uint32_t> &cnt, bin_scratch &t,
+                         std::vector<uint32_t> &esc, bool *delta)
+{
+    const uint64_t nnz = p.nnz, nseg = cnt.size();
+    {
+        device_buf<uint64_t> k64;
+        device_buf<uint32_t> idx;
+        SPMV_BUILD_TRY(k64.alloc(nnz));
+        SPMV_BUILD_TRY(t.k64s.alloc(nnz));
+        SPMV_BUILD_TRY(idx.alloc(nnz));
+        SPMV_BUILD_TRY(t.idxs.alloc(nnz));
+        SPMV_BUILD_TRY(launch_items(k_bin_key64, nnz, 256, s, t.key.get(), t.rowp.get(), nnz, k64.get(), idx.get()));
+        int end_bit = 17;
+        while (end_bit < 64 && (1ull << (end_bit - 16)) < nseg)
+            ++end_bit;
+        size_t tb = 0;
+        auto sort = [&](void *work) {
+            return hipcub::DeviceRadixSort::SortPairs(work, tb, k64.get(), t.k64s.get(), idx.get(), t.idxs.get(), nnz, 0,
+                                                      end_bit, s);
+        };
+        SPMV_BUILD_TRY(sort(nullptr));
+        SPMV_BUILD_TRY(t.tmp.alloc(tb));
+        SPMV_BUILD_TRY(sort(t.tmp.p));
+        // freed before the next allocations: the build's peak memory
+        SPMV_BUILD_TRY(k64.release());
+        SPMV_BUILD_TRY(idx.release());
+        SPMV_BUILD_TRY(t.tmp.release());
+    }
+    SPMV_BUILD_TRY(t.pads.alloc(nnz));
+    SPMV_BUILD_TRY(t.esc.alloc(std::max<uint64_t>(nseg, 1)));
+    SPMV_BUILD_TRY(hipMemsetAsync(t.esc, 0, std::max<uint64_t>(nseg, 1) * 4, s));
+    SPMV_BUILD_TRY(launch_items(k_bin_gaps, nnz, 256, s, t.k64s.get(), nnz, t.pads.get(), t.esc.get()));
+    SPMV_BUILD_TRY(hipMemcpyAsync(esc.data(), t.esc, nseg * 4, hipMemcpyDeviceToHost, s));
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
+    uint64_t total = 0;
+    for (uint32_t e : esc)
+        total += e;
+    *delta = always || total * 100 <= nnz;
+    if (!*delta) {
+        (void)t.k64s.release();
+        (void)t.idxs.release();
+        (void)t.pads.release();
+        (void)t.esc.release();
+        std::fill(esc.begin(), esc.end(), 0u);
+        return 0;
+    }
+    SPMV_BUILD_TRY(t.pscan.alloc(nnz));
+    size_t tb = 0;
+    SPMV_BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, t.pads.get(), t.pscan.get(), nnz, s));
+    SPMV_BUILD_TRY(t.tmp.alloc(tb));
+    SPMV_BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(t.tmp.p, tb, t.pads.get(), t.pscan.get(), nnz, s));
+    std::vector<uint64_t> soff(nseg + 1, 0);
+    for (uint64_t k = 0; k < nseg; ++k)
+        soff[k + 1] = soff[k] + cnt[k];
+    SPMV_BUILD_TRY(t.soff.alloc(nseg + 1));
+    SPMV_BUILD_TRY(hipMemcpyAsync(t.soff, soff.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Build step 3: the entries scattered into their padded segments, and the pad entries
+static int bin_scatter(spmv_plan &p, const IndexType *d_col_src, const ValueType *d_val_src, hipStream_t s,
+                       const std::vector<uint32_t> &esc, bin_scratch &t)
+{
+    const uint64_t nnz = p.nnz, nseg = esc.size();
+    const uint32_t P = (uint32_t)p.npanels;
+    if (p.b_delta) {
+        SPMV_BUILD_TRY(launch_items(k_bin_scatter_delta<ValueType>, nnz, 256, s, t.k64s.get(), t.idxs.get(),
+                                    t.pscan.get(), t.soff.get(), nnz, P, p.b_W, p.b_W1, d_col_src, d_val_src, p.d_b_seg,
+                                    p.d_b_val, p.d_b_colw, reinterpret_cast<uint8_t *>(p.d_b_rowp)));
+        SPMV_BUILD_TRY(hipMemcpyAsync(t.esc, esc.data(), nseg * 4, hipMemcpyHostToDevice, s));
+        SPMV_BUILD_TRY(launch_items(k_bin_pad<ValueType, true>, nseg, 256, s, nseg, p.d_b_seg, t.cnt.get(), t.esc.get(),
+                                    p.d_b_val, p.d_b_colw, (void *)p.d_b_rowp));
+    } else {
+        device_buf<uint32_t> cur;
+        SPMV_BUILD_TRY(cur.alloc(nseg));
+        SPMV_BUILD_TRY(hipMemsetAsync(cur, 0, nseg * 4, s));
+        SPMV_BUILD_TRY(launch_items(k_bin_scatter<ValueType>, nnz, 256, s, t.key.get(), t.rowp.get(), d_col_src, d_val_src,
+                                    nnz, P, p.b_W, p.b_W1, p.d_b_seg, cur.get(), p.d_b_val, p.d_b_colw,
+                                    reinterpret_cast<uint16_t *>(p.d_b_rowp)));
+        SPMV_BUILD_TRY(launch_items(k_bin_pad<ValueType, false>, nseg, 256, s, nseg, p.d_b_seg, t.cnt.get(),
+                                    (const uint32_t *)nullptr, p.d_b_val, p.d_b_colw, (void *)p.d_b_rowp));
+        SPMV_BUILD_TRY(hipStreamSynchronize(s));  // cur goes with the scope
+    }
+    return 0;
+}
+
+// The layout comes from the host planner (layout.cpp): windows (W columns, a whole number of rounds
+// of workgroups where x allows; plan_bin_windows), panels (nnz-balanced, <= rmax rows, whole
+// rounds; plan_panels), and after the counts the padded segment offsets and the pass-1 units
+// (plan_bin_units). This reads the switches, uploads the layout and runs the steps above. rc 2:
+// the segment table would be too large, or the matrix is skewed (the caller may use another kernel).
+int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, const ValueType *d_val_src,
+                 hipStream_t s)
+{
+    const IndexType n = p.nr_rows;
+    const uint64_t nnz = p.nnz;
+    const uint64_t cus = device_cu_count(p.device);
+    // Pass-1 XCC bias: unit u runs on XCC u % 8 (tools/xcc_map_probe.py), and on the boxes
+    // measured pass 1's one-window workgroups take 266 us on even XCCs against 280 us on odd ones
+    // (tools/wg_timeline.py --binned, profiles/r03bn_binned_timeline.jsonl). With one unit per
+    // window (nwin a whole number of rounds) even windows get W (1 + d) columns, odd ones
+    // W (1 - d): every pair still spans 2W, so a column's window stays closed-form
+    // (bin_win_of). Env SPMV_BIN_XCC_BIAS=d (0 = even widths); only on a whole 256-CU chip.
+    const char *xb = ablation_env("SPMV_BIN_XCC_BIAS");
+    const bin_windows win = plan_bin_windows(p.nr_cols, cus, xb ? std::atof(xb) : (cus == 256 ? kBinXccBias : 0.0));
+    // panels: y of <= rmax rows in LDS (fp64), plus the scratch slot of the pad entries
+    const uint32_t rmax = (uint32_t)std::min<uint64_t>((kSweepLdsBytes - 256) / 8 - 1, 65534);
+    panel_options po;
+    po.wgs = cus;
+    po.P_first = std::max<uint64_t>(min_panels(n, rmax), std::min<uint64_t>(cus, n));  // a round where n allows
+    panel_cut cut;
+    if (int rc = plan_panels(kWho, h_rp, n, nnz, rmax, po, cut))
+        return rc;
+    const std::vector<uint32_t> &prow = cut.prow;
+    const uint32_t P = (uint32_t)(prow.size() - 1);
+    if (int rc = bin_check_skew(p, h_rp, prow))
+        return rc;
+    const uint64_t nseg = win.nwin * P;
     if (nseg >= (1ull << 28)) {
         set_error("build_binned: too many (window, panel) segments");
         return 2;
     }
     p.npanels = P;
-    p.panel_rmax = rmax_used;
-    p.b_nwin = (uint32_t)nwin;
-    p.b_W = (uint32_t)W0;
-    p.b_W1 = (uint32_t)W1;
-    SPMV_TRY(hipMalloc((void **)&p.d_panel_row, (P + 1) * 4));
-    SPMV_TRY(hipMemcpyAsync(p.d_panel_row, prow.data(), (P + 1) * 4, hipMemcpyHostToDevice, s));
+    p.panel_rmax = 0;
+    for (uint32_t q = 0; q < P; ++q)
+        p.panel_rmax = std::max(p.panel_rmax, prow[q + 1] - prow[q]);
+    p.b_nwin = (uint32_t)win.nwin;
+    p.b_W = (uint32_t)win.W0;
+    p.b_W1 = (uint32_t)win.W1;
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_panel_row, (P + 1) * 4));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_panel_row, prow.data(), (P + 1) * 4, hipMemcpyHostToDevice, s));
 
-    IndexType *d_rp = nullptr;
-    uint32_t *d_key = nullptr, *d_cnt = nullptr, *d_cur = nullptr;
-    uint16_t *d_rowp_tmp = nullptr;
-    // delta layout temporaries
-    uint64_t *d_k64 = nullptr, *d_k64s = nullptr, *d_soff = nullptr;
-    uint32_t *d_idx = nullptr, *d_idxs = nullptr, *d_pads = nullptr, *d_pscan = nullptr, *d_esc = nullptr;
-    void *d_tmp = nullptr;
-    auto free_delta = [&]() {
-        for (void **q : {(void **)&d_k64, (void **)&d_k64s, (void **)&d_soff, (void **)&d_idx, (void **)&d_idxs,
-                         (void **)&d_pads, (void **)&d_pscan, (void **)&d_esc, &d_tmp})
-            if (*q) {
-                (void)hipFree(*q);
-                *q = nullptr;
-            }
-    };
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_rp, (void *)d_key, (void *)d_cnt, (void *)d_cur, (void *)d_rowp_tmp})
-            if (q)
-                (void)hipFree(q);
-        free_delta();
-    };
-    auto fail = [&](hipError_t e, const char *what) {
-        set_error(std::string("build_binned: ") + what + ": " + hipGetErrorString(e));
-        cleanup();
-        return 1;
-    };
-#define BN_TRY(x)                              \
-    do {                                       \
-        hipError_t e_ = (x);                   \
-        if (e_ != hipSuccess)                  \
-            return fail(e_, #x);               \
-    } while (0)
-    std::vector<uint32_t> cnt(nseg, 0);
-    BN_TRY(hipMalloc((void **)&d_cnt, std::max<uint64_t>(nseg, 1) * 4));
-    BN_TRY(hipMemsetAsync(d_cnt, 0, std::max<uint64_t>(nseg, 1) * 4, s));
-    if (nnz) {
-        BN_TRY(hipMalloc((void **)&d_rp, (size_t(n) + 1) * 4));
-        BN_TRY(hipMemcpyAsync(d_rp, h_rp, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
-        BN_TRY(hipMalloc((void **)&d_key, nnz * 4));
-        BN_TRY(hipMalloc((void **)&d_rowp_tmp, nnz * 2));
-        hipLaunchKernelGGL(k_bin_keys, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, d_rp, n, d_col_src, nnz,
-                           p.d_panel_row, P, (uint32_t)W0, (uint32_t)W1, d_key, d_rowp_tmp, d_cnt);
-        BN_TRY(hipGetLastError());
-        BN_TRY(hipMemcpyAsync(cnt.data(), d_cnt, nseg * 4, hipMemcpyDeviceToHost, s));
-        BN_TRY(hipStreamSynchronize(s));
-    }
+    bin_scratch t;
+    std::vector<uint32_t> cnt(nseg, 0), esc(nseg, 0);
+    if (int rc = bin_count(p, h_rp, d_col_src, s, t, cnt))
+        return rc;
     // Delta layout (env SPMV_BIN_DELTA: 0 never, 1 always, default when its escape entries stay
     // under 1 % of nnz): each segment sorted by row, 1-byte row deltas, pass 2 reading 1 B less
     // per non-zero (tools/delta_probe.hip: pass 2 0.159 vs 0.180 ms on the 10M/160M fp32 shape).
     // Sparse segments (small matrices, gaps over 255 rows) would need many escapes: u16 offsets.
-    std::vector<uint32_t> esc(nseg, 0);
-    bool delta = false;
-    {
-        const char *denv = ablation_env("SPMV_BIN_DELTA");
-        const bool never = denv && denv[0] == '0', always = denv && denv[0] == '1';
-        delta = !nnz && always;  // an empty slice: either form reads nothing
-        if (nnz && !never) {
-            BN_TRY(hipMalloc((void **)&d_k64, nnz * 8));
-            BN_TRY(hipMalloc((void **)&d_k64s, nnz * 8));
-            BN_TRY(hipMalloc((void **)&d_idx, nnz * 4));
-            BN_TRY(hipMalloc((void **)&d_idxs, nnz * 4));
-            hipLaunchKernelGGL(k_bin_key64, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, d_key, d_rowp_tmp,
-                               nnz, d_k64, d_idx);
-            BN_TRY(hipGetLastError());
-            int end_bit = 17;
-            while (end_bit < 64 && (1ull << (end_bit - 16)) < nseg)
-                ++end_bit;
-            size_t tb = 0;
-            BN_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, d_k64, d_k64s, d_idx, d_idxs, nnz, 0, end_bit, s));
-            BN_TRY(hipMalloc(&d_tmp, tb));
-            BN_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_k64, d_k64s, d_idx, d_idxs, nnz, 0, end_bit, s));
-            BN_TRY(hipFree(d_k64));
-            d_k64 = nullptr;
-            BN_TRY(hipFree(d_idx));
-            d_idx = nullptr;
-            BN_TRY(hipFree(d_tmp));
-            d_tmp = nullptr;
-            BN_TRY(hipMalloc((void **)&d_pads, nnz * 4));
-            BN_TRY(hipMalloc((void **)&d_esc, std::max<uint64_t>(nseg, 1) * 4));
-            BN_TRY(hipMemsetAsync(d_esc, 0, std::max<uint64_t>(nseg, 1) * 4, s));
-            hipLaunchKernelGGL(k_bin_gaps, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, d_k64s, nnz, d_pads,
-                               d_esc);
-            BN_TRY(hipGetLastError());
-            BN_TRY(hipMemcpyAsync(esc.data(), d_esc, nseg * 4, hipMemcpyDeviceToHost, s));
-            BN_TRY(hipStreamSynchronize(s));
-            uint64_t total = 0;
-            for (uint32_t e : esc)
-                total += e;
-            delta = always || total * 100 <= nnz;
-            if (delta) {
-                BN_TRY(hipMalloc((void **)&d_pscan, nnz * 4));
-                tb = 0;
-                BN_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_pads, d_pscan, nnz, s));
-                BN_TRY(hipMalloc(&d_tmp, tb));
-                BN_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_pads, d_pscan, nnz, s));
-                std::vector<uint64_t> soff(nseg + 1, 0);
-                for (uint64_t k = 0; k < nseg; ++k)
-                    soff[k + 1] = soff[k] + cnt[k];
-                BN_TRY(hipMalloc((void **)&d_soff, (nseg + 1) * 8));
-                BN_TRY(hipMemcpyAsync(d_soff, soff.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, s));
-                BN_TRY(hipStreamSynchronize(s));
-            } else {
-                free_delta();
-                std::fill(esc.begin(), esc.end(), 0u);
-            }
-        }
-    }
+    const char *denv = ablation_env("SPMV_BIN_DELTA");
+    const bool never = denv && denv[0] == '0', always = denv && denv[0] == '1';
+    bool delta = !nnz && always;  // an empty slice: either form reads nothing
+    if (nnz && !never)
+        if (int rc = bin_sort_rows(p, s, always, cnt, t, esc, &delta))
+            return rc;
     p.b_delta = delta;
-    // padded segment offsets (window-major), then the pass-1 units
-    // Each window's range also starts on a 128-entry boundary (the last segment of the window
-    // takes the extra pad entries): pass 1's 1-KiB wave loads and stores then cover whole
-    // 128-byte lines instead of straddling them (partial-line stores).
-    std::vector<uint64_t> seg(nseg + 1, 0);
-    for (uint64_t k = 0; k < nseg; ++k) {
-        seg[k + 1] = seg[k] + (uint64_t(cnt[k]) + esc[k] + PER - 1) / PER * PER;
-        if ((k + 1) % P == 0)
-            seg[k + 1] = (seg[k + 1] + kBinAlign - 1) / kBinAlign * kBinAlign;
-    }
-    const uint64_t ent_pad = seg[nseg];
+    bin_units bu;
+    plan_bin_units(cnt, esc, win.nwin, P, cus, bu);
+    const uint64_t ent_pad = bu.seg[nseg];
     p.ent_pad = ent_pad;
     p.b_prod_temporal = ent_pad * sizeof(ValueType) <= (1ull << 30);
-    std::vector<uint64_t> ub(1, 0);
-    std::vector<uint32_t> uwin;
-    {
-        const double mean = nwin ? double(ent_pad) / double(nwin) : 0.0;
-        const uint64_t fill = nwin < (uint64_t)cus ? (cus + nwin - 1) / nwin : 1;  // few windows: pieces
-        for (uint64_t w = 0; w < nwin; ++w) {
-            const uint64_t a = seg[w * P], b = seg[(w + 1) * P], e = b - a;
-            if (!e)
-                continue;
-            uint64_t k = std::max<uint64_t>(fill, (uint64_t)std::ceil(double(e) / std::max(2.0 * mean, 1.0)));
-            k = std::max<uint64_t>(1, std::min<uint64_t>(k, e / kBinAlign));  // e: whole 128-entry groups
-            ub.back() = a;
-            for (uint64_t t = 1; t <= k; ++t) {
-                ub.push_back(a + (e / kBinAlign) * t / k * kBinAlign);
-                uwin.push_back((uint32_t)w);
-            }
-        }
-    }
-    p.b_nunits = uwin.size();
-    BN_TRY(hipMalloc((void **)&p.d_b_seg, (nseg + 1) * 8));
-    BN_TRY(hipMemcpyAsync(p.d_b_seg, seg.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, s));
-    BN_TRY(hipMalloc((void **)&p.d_b_ub, ub.size() * 8));
-    BN_TRY(hipMemcpyAsync(p.d_b_ub, ub.data(), ub.size() * 8, hipMemcpyHostToDevice, s));
-    BN_TRY(hipMalloc((void **)&p.d_b_uwin, std::max<size_t>(uwin.size(), 1) * 4));
-    if (!uwin.empty())
-        BN_TRY(hipMemcpyAsync(p.d_b_uwin, uwin.data(), uwin.size() * 4, hipMemcpyHostToDevice, s));
-    const uint64_t alloc = std::max<uint64_t>(ent_pad, PER);
-    BN_TRY(hipMalloc((void **)&p.d_b_val, alloc * sizeof(ValueType)));
+    p.b_nunits = bu.uwin.size();
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_seg, (nseg + 1) * 8));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_b_seg, bu.seg.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_ub, bu.ub.size() * 8));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_b_ub, bu.ub.data(), bu.ub.size() * 8, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_uwin, std::max<size_t>(bu.uwin.size(), 1) * 4));
+    if (!bu.uwin.empty())
+        SPMV_BUILD_TRY(hipMemcpyAsync(p.d_b_uwin, bu.uwin.data(), bu.uwin.size() * 4, hipMemcpyHostToDevice, s));
+    const uint64_t alloc = std::max<uint64_t>(ent_pad, kBinPer);
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_val, alloc * sizeof(ValueType)));
     {
         // env SPMV_BIN_PROD_SKEW=bytes (measurement): the products start that far (a multiple of
         // 256 B) into their allocation, shifting their address bits against the entry arrays'
         const char *sk = ablation_env("SPMV_BIN_PROD_SKEW");
         const uint64_t skew = sk ? (uint64_t)std::strtoull(sk, nullptr, 10) / 256 * 256 : 0;
-        BN_TRY(hipMalloc(&p.d_b_prod_alloc, alloc * sizeof(ValueType) + skew));
+        SPMV_BUILD_TRY(hipMalloc(&p.d_b_prod_alloc, alloc * sizeof(ValueType) + skew));
         p.d_b_prod = reinterpret_cast<ValueType *>(static_cast<unsigned char *>(p.d_b_prod_alloc) + skew);
     }
-    BN_TRY(hipMalloc((void **)&p.d_b_colw, alloc * 2));
-    BN_TRY(hipMalloc((void **)&p.d_b_rowp, alloc * (delta ? 1 : 2)));
-    if (nnz && delta) {
-        hipLaunchKernelGGL((k_bin_scatter_delta<ValueType>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s,
-                           d_k64s, d_idxs, d_pscan, d_soff, nnz, P, (uint32_t)W0, (uint32_t)W1, d_col_src, d_val_src, p.d_b_seg,
-                           p.d_b_val, p.d_b_colw, reinterpret_cast<uint8_t *>(p.d_b_rowp));
-        BN_TRY(hipGetLastError());
-        BN_TRY(hipMemcpyAsync(d_esc, esc.data(), nseg * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL((k_bin_pad<ValueType, true>), dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, s, nseg,
-                           p.d_b_seg, d_cnt, d_esc, p.d_b_val, p.d_b_colw, (void *)p.d_b_rowp);
-        BN_TRY(hipGetLastError());
-    } else if (nnz) {
-        BN_TRY(hipMalloc((void **)&d_cur, nseg * 4));
-        BN_TRY(hipMemsetAsync(d_cur, 0, nseg * 4, s));
-        hipLaunchKernelGGL((k_bin_scatter<ValueType>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, d_key,
-                           d_rowp_tmp, d_col_src, d_val_src, nnz, P, (uint32_t)W0, (uint32_t)W1, p.d_b_seg, d_cur, p.d_b_val,
-                           p.d_b_colw, reinterpret_cast<uint16_t *>(p.d_b_rowp));
-        BN_TRY(hipGetLastError());
-        hipLaunchKernelGGL((k_bin_pad<ValueType, false>), dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0, s, nseg,
-                           p.d_b_seg, d_cnt, (const uint32_t *)nullptr, p.d_b_val, p.d_b_colw, (void *)p.d_b_rowp);
-        BN_TRY(hipGetLastError());
-    }
-    BN_TRY(hipStreamSynchronize(s));
-    cleanup();
-#undef BN_TRY
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_colw, alloc * 2));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_rowp, alloc * (delta ? 1 : 2)));
+    if (nnz)
+        if (int rc = bin_scatter(p, d_col_src, d_val_src, s, esc, t))
+            return rc;
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
     return 0;
 }
 

@@ -1,7 +1,8 @@
 // Host-only parts of libspmv_hw (no HIP calls): the error channel, the CSR-slice front end of the
 // create calls (argument checks, rebased row_ptr), the nnz-balanced row partition, the exchange schedule of the multi-GPU merge, the threaded accum_results '+=',
-// verification and storage_overhead. Besides the product library, tests/sanitize/Makefile builds
-// this file and reader.cpp with g++ under AddressSanitizer + UBSan and under ThreadSanitizer
+// verification and storage_overhead. The layout planner of the sweep and binned builds is host-only
+// too (layout.cpp). Besides the product library, tests/sanitize/Makefile builds
+// this file, layout.cpp and reader.cpp with g++ under AddressSanitizer + UBSan and under ThreadSanitizer
 // (SURVEY §5 "sanitizers").
 #include <sys/mman.h>
 #include <sys/time.h>

@@ -1,8 +1,9 @@
-// Host-only internals of libspmv_hw (no HIP): what host.cpp and reader.cpp share with the rest of
-// the library. tests/sanitize/Makefile compiles these two sources with g++ -fsanitize=... into a
+// Host-only internals of libspmv_hw (no HIP): what host.cpp, layout.cpp and reader.cpp share with the
+// rest of the library. tests/sanitize/Makefile compiles these three sources with g++ -fsanitize=... into a
 // host-only check program, so nothing here may need the HIP headers.
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -54,6 +55,70 @@ int slice_device_args(const char *who, const void *handle, IndexType n, const In
 // s.val the caller's arrays: subtracts rp[0], checks rp[n] against *nr_nzeros when given (the
 // message names <who>), offsets col / val and checks that rp does not decrease.
 int slice_rebase(const char *who, csr_slice &s, const IndexType *nr_nzeros = nullptr);
+
+// Layout planner of the panel-sweep and binned builds (layout.cpp): the host arithmetic that decides
+// a plan's panels, work units, windows and segments. Pure functions of their arguments: no HIP and
+// no environment -- build_sweep / build_binned read the switches and pass them in.
+constexpr uint64_t kSweepLdsBytes = 160 * 1024;       // LDS of one CU holds the panel's y
+constexpr uint64_t kSweepChunk = 128;                 // entries per packed chunk (one wave, 2 per lane)
+constexpr uint32_t kBinPer = 16 / sizeof(ValueType);  // binned: entries per 16-byte vector
+constexpr uint64_t kBinAlign = 128;  // binned, entries: window ranges and pass-1 units start at multiples
+
+// the fewest panels of at most rmax rows that hold n rows
+inline uint64_t min_panels(uint64_t n, uint32_t rmax) { return std::max<uint64_t>(1, (n + rmax - 1) / rmax); }
+
+struct panel_options {
+    uint64_t wgs = 256;        // resident workgroups per round: multi-panel cuts are whole rounds
+    uint64_t P_first = 1;      // the first panel count to try
+    bool allow_split = false;  // split mode (few full-size panels, each cut into pieces) may be chosen,
+    bool force_split = false;  // or is whenever at least 2 pieces per panel fit
+    uint64_t acc_bytes = 8, val_bytes = sizeof(ValueType);  // split mode's cost test: a partial sum, a value
+    double xbias = 0.0;        // even / odd panel bias of the cut (0: even cut)
+};
+struct panel_cut {
+    std::vector<uint32_t> prow;  // first row of each panel, and n
+    bool split_mode = false;
+    double xbias = 0.0;          // the bias the cut was made with (0 after a fallback to the even cut)
+};
+// nnz-balanced panels of at most rmax rows: panel q ends at the first row whose start reaches q/P of
+// the entries (weighted by the bias), P searched upwards from P_first in whole rounds.
+// Returns 0, or 1 with the error "<who>: cannot form panels".
+int plan_panels(const char *who, const IndexType *h_rp, IndexType n, uint64_t nnz, uint32_t rmax,
+                const panel_options &o, panel_cut &out);
+
+struct sweep_units {
+    std::vector<uint32_t> off, poff;  // first entry of each panel: in CSR order, padded to whole chunks
+    std::vector<uint32_t> punit;      // first unit of each panel [P + 1]
+    std::vector<uint32_t> upanel;     // panel of each unit (one slot when there is none)
+    std::vector<uint32_t> uent;       // first padded entry of each unit [U + 1]
+    uint32_t rmax_used = 0;           // rows of the largest panel
+    uint32_t sweep_split = 1;         // > 1: some panel has several units (combine needed)
+    double xbias_split = 0.0;         // the bias the pieces were cut with
+};
+// The sweep's work units over the panels `prow`: whole chunks of each panel's padded entries, in split
+// mode `wgs / P` pieces per panel (pieces_override > 0: that many) cut with the even / odd bias
+// `xbias_split`. Returns 0, or 2 with the error "<who>: padded entry count exceeds 32 bits".
+int plan_sweep_units(const char *who, const IndexType *h_rp, const std::vector<uint32_t> &prow, bool split_mode,
+                     uint64_t wgs, int pieces_override, double xbias_split, sweep_units &out);
+
+// Binned's column windows: nwin of them, at most wmax columns (LDS, u16 offsets), multiples of
+// kBinPer, whole rounds of `cus` workgroups where ncols allows. Even windows are W0 wide, odd ones
+// W1 (W0 + W1 = 2 W): the bias d widens the even ones to W (1 + d) when nwin is whole rounds and
+// both widths fit.
+struct bin_windows {
+    uint64_t wmax = 0, nwin = 1, W = kBinPer, W0 = kBinPer, W1 = kBinPer;
+};
+bin_windows plan_bin_windows(uint64_t ncols, uint64_t cus, double d);
+
+// Binned's segments (cnt + esc entries each, padded to kBinPer, every window starting on a kBinAlign
+// boundary) and the pass-1 units of whole kBinAlign groups over the non-empty windows.
+struct bin_units {
+    std::vector<uint64_t> seg;   // padded (window, panel) segment offsets, window-major [nwin P + 1]
+    std::vector<uint64_t> ub;    // pass-1 unit boundaries [units + 1]
+    std::vector<uint32_t> uwin;  // window of each pass-1 unit
+};
+void plan_bin_units(const std::vector<uint32_t> &cnt, const std::vector<uint32_t> &esc, uint64_t nwin, uint64_t P,
+                    uint64_t cus, bin_units &out);
 
 // wall clock in microseconds (util.cpp:3-8)
 double timestamp_us();

@@ -39,8 +39,6 @@ constexpr int kTileSteps = 2;                      // wave steps per tile
 constexpr int kTileNnz = kStep * kTileSteps;       // 512 entries per wave tile
 constexpr int kBlockThreads = 256;                 // 4 waves = 4 tiles per workgroup
 constexpr int kSweepThreads = 1024;                // default panel-sweep workgroup (16 waves, 1/CU)
-constexpr uint64_t kSweepLdsBytes = 160 * 1024;    // LDS of one CU holds the panel's y
-constexpr uint64_t kSweepChunk = 128;              // entries per packed chunk (one wave, 2 per lane)
 constexpr int kSweepTurn = 91;         // sweep variant: ordered LDS adds (deterministic y), the
 constexpr int kSweepTurnOrdered = 94;  // form of SPMV_SWEEP_DETERMINISTIC=1; 94: adds awaited
 
@@ -316,6 +314,43 @@ struct device_scratch {
             (void)hipFree(p);
     }
 };
+// ... of `count` elements of T. release() frees early (where that bounds a build's peak memory);
+// swap() trades the buffer with one the plan owns, so the scratch frees what the plan held
+template <typename T>
+struct device_buf : device_scratch {
+    device_buf() = default;
+    device_buf(const device_buf &) = delete;  // one owner (a kernel argument is get(), never the buffer)
+    T *get() const { return static_cast<T *>(p); }
+    operator T *() const { return get(); }
+    hipError_t alloc(uint64_t count) { return hipMalloc(&p, count * sizeof(T)); }
+    hipError_t release()
+    {
+        void *q = p;
+        p = nullptr;
+        return q ? hipFree(q) : hipSuccess;
+    }
+    void swap(T *&owned)
+    {
+        T *q = get();
+        p = owned;
+        owned = q;
+    }
+};
+// a kernel over `items` threads in blocks of `block`; the launch's error
+template <typename K, typename... Args>
+inline hipError_t launch_items(K kernel, uint64_t items, unsigned block, hipStream_t s, Args... args)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((items + block - 1) / block)), dim3(block), 0, s, args...);
+    return hipGetLastError();
+}
+// compute units of the device (256 when the query fails)
+inline int device_cu_count(int device)
+{
+    hipDeviceProp_t prop;
+    return hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0
+               ? prop.multiProcessorCount
+               : 256;
+}
 
 // plan.cpp helpers shared with the wrapper
 int upload_staged(void *dst, const void *src, size_t bytes, hipStream_t s);  // pageable H2D, synchronous
@@ -367,4 +402,13 @@ int mgpu_rccl_calls(const spmv_mgpu *mg);  // RCCL calls per step of the last ru
             spmvhw::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));             \
             return 1;                                                                         \
         }                                                                                     \
+    } while (0)
+// the same inside a plan build and its steps, "<build>: <expr>: <hip error>": the file's kWho names the build
+#define SPMV_BUILD_TRY(expr)                                                                          \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) {                                                                       \
+            spmvhw::set_error(std::string(kWho) + ": " + #expr + ": " + hipGetErrorString(e_));       \
+            return 1;                                                                                 \
+        }                                                                                             \
     } while (0)

@@ -1403,223 +1403,17 @@ hipError_t launch_sweep(const spmv_plan &p, const ValueType *d_x, ValueType *d_y
     return hipGetLastError();
 }
 
-// The pieces of every panel: whole chunks, cut with the even / odd XCC bias d (the weight of
-// units [0, u) is u - d (u & 1): the units block-round-robin dispatch sends to even XCCs get
-// (1 - d) x the mean, the odd ones (1 + d) x); d = 0 cuts evenly
-static void cut_units(const std::vector<uint32_t> &poff, const std::vector<uint32_t> &punit, double d,
-                      std::vector<uint32_t> &uent)
-{
-    const uint32_t P = (uint32_t)punit.size() - 1, U = punit[P];
-    uent.assign((size_t)U + 1, 0);
-    auto wc = [&](uint32_t u) { return double(u) - d * double(u & 1); };
-    for (uint32_t q = 0; q < P; ++q) {
-        const uint64_t chunks = (uint64_t(poff[q + 1]) - poff[q]) / kSweepChunk;
-        const uint32_t k = punit[q + 1] - punit[q], u0 = punit[q];
-        for (uint32_t t = 0; t < k; ++t) {
-            const uint64_t c = d != 0.0 ? (uint64_t)(double(chunks) * (wc(u0 + t) - wc(u0)) / (wc(u0 + k) - wc(u0)))
-                                        : chunks * t / k;
-            uent[u0 + t] = (uint32_t)(poff[q] + kSweepChunk * c);
-        }
-    }
-    uent[U] = poff[P];
-}
+static const char kWho[] = "build_sweep";
 
-// Host: panel boundaries (nnz-balanced, <= rmax rows each), then the device sort + scatter.
-// Work units: when the slice has at least one panel per resident workgroup, panels are rounded
-// to whole rounds of workgroups and each panel is one unit. When it has fewer (a slice of fewer
-// than ~5M rows), the panels keep their full LDS size and each is cut into `split` pieces of
-// whole chunks of its column-sorted entries (contiguous column ranges, equal entry counts) --
-// the reference's 2-D blocking (row slices x column blocks, csr_hw.cpp:25-76) with the column
-// blocks sized by work. Denser panels touch fewer x lines per non-zero; the pieces' fp64
-// partial sums go to a scratch array and k_sweep_combine adds them per row in piece order
-// (env SPMV_SWEEP_SPLIT=0 keeps the smaller-panel form).
-int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, const ValueType *d_val_src,
-                hipStream_t s)
+// Build step 1: every panel's entries in column order. A key (panel, column bucket) per entry, a
+// radix sort, the scatter into the panels' padded ranges, and the pad entries.
+static int sweep_sort_entries(spmv_plan &p, const sweep_units &u, const IndexType *h_rp, const IndexType *d_col_src,
+                              const ValueType *d_val_src, hipStream_t s)
 {
     const IndexType n = p.nr_rows;
     const uint64_t nnz = p.nnz;
-    // a workgroup of T threads gets T/1024 of one CU's LDS for its panel's y
-    const uint64_t lds_bytes = kSweepLdsBytes * p.sweep_threads / 1024 - 256;  // 256 B: static LDS
-    // accumulator: fp64, or fp32 (compare-and-swap adds) for fp32 matrices with env SPMV_SWEEP_ACC=32
-    const char *aenv = ablation_env("SPMV_SWEEP_ACC");
-    p.sweep_acc_bytes = sizeof(ValueType) == 4 && aenv && std::atoi(aenv) == 32 ? 4 : 8;
-    const uint64_t acc = p.sweep_acc_bytes;
-    const uint32_t rmax = (uint32_t)std::min<uint64_t>(lds_bytes / acc - 1, 65534);
-    int cus = 256;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, p.device) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-    }
-    const int chip_cus = cus;
-    cus *= 1024 / p.sweep_threads;  // resident workgroups per round
-    // env SPMV_SWEEP_SPLIT: 0 = never split, 2 = split whenever >= 2 pieces fit, else heuristic
-    const char *senv = ablation_env("SPMV_SWEEP_SPLIT");
-    // env SPMV_SWEEP_DETERMINISTIC=1: the same layout, run by k_spmv_sweep_turn (ordered adds)
-    const char *denv = std::getenv("SPMV_SWEEP_DETERMINISTIC");
-    const bool det = denv && denv[0] == '1';
-    const bool allow_split = !(senv && senv[0] == '0');
-    const bool force_split = senv && senv[0] == '2';
-    bool split_mode = false;
-    // XCC bias: the units the round-robin dispatch sends to even XCCs (unit % 8 even; block b
-    // runs on XCC b % 8 in every launch probed, tools/xcc_map_probe.py) get (1 - d) x the mean
-    // entries, the odd ones (1 + d) x; weight of the units [0, u): u - d * (u & 1). Why: on the
-    // MI355X boxes measured, workgroups on even XCCs sweep 2-4 % slower than on odd ones, in the
-    // whole matrix and in the strong-scaling slices (tools/wg_timeline.py,
-    // profiles/r03ay_wg_timeline.jsonl, two boxes), and the launch ends with the slowest XCC.
-    // Defaults on a whole chip (256 CUs = 8 XCDs): d = 0.015 for whole panels, 0.02 for split
-    // pieces (interleaved A/B, profiles/r03bb_xcc_bias.jsonl: 10M/160M -1.3 %, the N = 8 slice
-    // -2.0 %, N = 4 -0.7 %); env SPMV_SWEEP_XCC_BIAS=d overrides both (0 = even cut).
-    // Split pieces (the N >= 4 strong-scaling slices) are cut evenly by default: which XCCs
-    // sweep slower varies from box to box (even ones on the boxes of round 3, odd ones on some of
-    // round 4), and the even cut was within 1 % of a per-GPU timed pick and ahead of the fixed
-    // 2 % bias at N = 4 (profiles/r04w_xcc_bias_ab.jsonl, r04y), a tie at N = 8. The cut is a
-    // function of the matrix and the chip's CU count only, like the reference's (csr_hw.cpp:459-468).
-    const char *xbenv = std::getenv("SPMV_SWEEP_XCC_BIAS");
-    double xbias_split = xbenv ? std::atof(xbenv) : 0.0;
-    double xbias = xbenv ? std::atof(xbenv) : chip_cus == 256 ? 0.015 : 0.0;
-    if (!(xbias > -0.5 && xbias < 0.5))
-        xbias = xbias_split = 0.0;
-    std::vector<uint32_t> prow;
-    // subdivide: a run of (nearly) empty rows longer than a panel that no nnz-balanced cut reaches
-    // -- most often trailing empty rows -- made every P fail (and the search ran on to P = n);
-    // after a bounded search the cuts are taken at the first P and any panel above the LDS rows is
-    // split into panels of at most rmax rows
-    const uint64_t P_first = std::max<uint64_t>(1, (n + rmax - 1) / rmax);
-    uint64_t P_start = P_first;
-    // (tools build) SPMV_SWEEP_ROUNDS=k: at least k rounds of whole panels on a matrix that fills
-    // a round anyway (smaller panels: earlier first panels for a streamed copy-back)
-    if (const char *ke = ablation_env("SPMV_SWEEP_ROUNDS"); ke && std::atoi(ke) > 0 && P_first * 2 >= (uint64_t)cus)
-        P_start = std::max<uint64_t>(P_first, (uint64_t)std::min(std::atoi(ke), 8) * cus);
-    bool subdivide = false;
-    for (uint64_t P = P_start;; ++P) {
-        {
-            // pieces pay when the slice fills at most half the workgroups with full panels and
-            // the partial sums (split * n fp64 values, written once and read once by the
-            // combine) stay below 0.6x the entry stream. Measured (profiles/): a 1M-row
-            // power-law matrix 14 % faster (partials 0.42x the entries), the N = 8 slice of
-            // the 10M/160M matrix 18 % (0.33x), a 300K-row matrix 25 % slower (1.4x)
-            const uint64_t S = P ? (uint64_t)cus / P : 0;
-            split_mode = !subdivide && allow_split && S >= 2 && P * S * 10 >= (uint64_t)cus * 9 &&
-                         (force_split || 2 * S * n * acc * 5 <= 3 * nnz * (4 + sizeof(ValueType)));
-        }
-        if (!split_mode && P > 1 && P % cus)
-            P = (P + cus - 1) / cus * cus;  // whole rounds of workgroups
-        P = std::min<uint64_t>(P, std::max<uint64_t>(n, 1));
-        prow.assign(1, 0);
-        bool ok = true;
-        IndexType r = 0;
-        for (uint64_t q = 1; q <= P && ok; ++q) {
-            const uint64_t target =
-                split_mode || xbias == 0.0
-                    ? nnz * q / P
-                    : (uint64_t)(double(nnz) * (double(q) - xbias * double(q & 1)) / (double(P) - xbias * double(P & 1)));
-            IndexType e = (q == P) ? n : (IndexType)(std::lower_bound(h_rp, h_rp + n + 1, (IndexType)target) - h_rp);
-            e = std::max(e, r);
-            if (e - r > rmax && xbias != 0.0 && !split_mode && q < P)
-                e = r + rmax;  // a biased cut past the LDS rows: this panel takes what fits
-            if (e - r > rmax && subdivide)
-                for (; e - r > rmax; r += rmax)
-                    prow.push_back(r + rmax);
-            if (e - r > rmax)
-                ok = false;
-            prow.push_back(e);
-            r = e;
-        }
-        if (ok)
-            break;
-        if (xbias != 0.0 && !split_mode) {  // the biased cut overflows a panel: cut evenly
-            xbias = 0.0;
-            --P;
-            continue;
-        }
-        if (P >= n || P > 8 * std::max<uint64_t>(P_first, (uint64_t)cus)) {
-            if (subdivide) {
-                set_error("build_sweep: cannot form panels");
-                return 1;
-            }
-            subdivide = true;
-            xbias = 0.0;
-            P = P_start - 1;  // (++P)
-        }
-    }
-    const uint32_t P = (uint32_t)(prow.size() - 1);
-    if (split_mode)
-        xbias = xbias_split;  // the pieces' cut below (the panels were cut evenly)
-    const std::vector<uint32_t> &srow = prow;  // sort segments = the panels
-    const uint32_t S = (uint32_t)(srow.size() - 1);
-    std::vector<uint32_t> off(S + 1), poff(S + 1);
-    off[0] = poff[0] = 0;
-    uint32_t rmax_used = 0;
-    uint64_t padded = 0;
-    for (uint32_t q = 0; q < S; ++q) {
-        const uint64_t cnt = uint64_t(h_rp[srow[q + 1]]) - h_rp[srow[q]];
-        padded += (cnt + kSweepChunk - 1) / kSweepChunk * kSweepChunk;
-        off[q + 1] = (uint32_t)(off[q] + cnt);
-        poff[q + 1] = (uint32_t)padded;
-    }
-    for (uint32_t q = 0; q < P; ++q)
-        rmax_used = std::max(rmax_used, prow[q + 1] - prow[q]);
-    if (padded > 0xFFFFFFFFull) {  // panel_ent is u32: the padded layout must fit (nnz near 2^32)
-        set_error("build_sweep: padded entry count exceeds 32 bits");
-        return 2;
-    }
-    p.npanels = P;
-    p.panel_rmax = rmax_used;
-    p.ent_pad = poff[S];
-    p.sweep_det = det;
-    // work units: pieces of whole chunks per panel. split mode: `split` pieces each; any panel
-    // with more than twice the mean entry count (a panel holding very long rows) is cut
-    // further, so that no workgroup gets more than ~2x the mean work
-    uint32_t split = split_mode ? std::max<uint32_t>(1, (uint32_t)cus / P) : 1;
-    // env SPMV_SWEEP_PIECES=k (experiments): k pieces per panel in split mode instead of cus / P
-    if (const char *kenv = ablation_env("SPMV_SWEEP_PIECES"); split_mode && kenv && std::atoi(kenv) > 0)
-        split = (uint32_t)std::atoi(kenv);
-    const double mean = P ? double(padded) / P : 0.0;
-    std::vector<uint32_t> punit(P + 1, 0);
-    for (uint32_t q = 0; q < P; ++q) {
-        const uint64_t chunks = (uint64_t(poff[q + 1]) - poff[q]) / kSweepChunk;
-        uint64_t k = split * std::max<uint64_t>(
-                                 1, (uint64_t)std::ceil(double(poff[q + 1] - poff[q]) / std::max(2.0 * mean, 1.0)));
-        k = std::max<uint64_t>(1, std::min<uint64_t>(k, chunks));
-        punit[q + 1] = punit[q] + (uint32_t)k;
-    }
-    const uint32_t U = punit[P];
-    std::vector<uint32_t> uent, upanel(std::max<uint32_t>(U, 1));
-    bool multi = false;
-    for (uint32_t q = 0; q < P; ++q) {
-        multi |= punit[q + 1] - punit[q] > 1;
-        for (uint32_t u = punit[q]; u < punit[q + 1]; ++u)
-            upanel[u] = q;
-    }
-    cut_units(poff, punit, split_mode ? xbias : 0.0, uent);
-    p.xbias_split = split_mode ? xbias : 0.0;
-    p.sweep_split = multi ? std::max<uint32_t>(split, 2) : 1;  // > 1: combine kernel needed
-    p.nunits = U;
-    if (multi) {
-        SPMV_TRY(hipMalloc((void **)&p.d_part, (uint64_t)U * (uint64_t(rmax_used) + 1) * acc));
-#ifdef SPMV_ABLATIONS
-        // work-stealing counters of the measurement variants (zero; every k_sweep_combine re-arms them)
-        SPMV_TRY(hipMalloc((void **)&p.d_steal, (uint64_t)U * 8));
-        SPMV_TRY(hipMemsetAsync(p.d_steal, 0, (uint64_t)U * 8, s));
-#endif
-        // env SPMV_SWEEP_COMBINE=fused: the last piece of each panel combines inside the sweep
-        // launch instead of k_sweep_combine. Measured slower on the N = 8 slice of the 10M/160M
-        // matrix (0.147 vs 0.128 ms, profiles/r03_ab_sweep_combine.jsonl): the panels of a one-round
-        // launch all finish together, and each last arriver then reads its 4 x 160 KiB of partials
-        // alone (~50-70 GB/s per workgroup, MI355X_MICROARCH.md handoff-payload) where the combine
-        // kernel reads them with the whole chip; so the separate launch stays the default
-        const char *cenv = ablation_env("SPMV_SWEEP_COMBINE");
-        if (cenv && std::strcmp(cenv, "fused") == 0) {
-            SPMV_TRY(hipMalloc((void **)&p.d_panel_cnt, std::max<uint64_t>(P, 1) * 4));
-            SPMV_TRY(hipMemsetAsync(p.d_panel_cnt, 0, std::max<uint64_t>(P, 1) * 4, s));
-        }
-    }
-    SPMV_TRY(hipMalloc((void **)&p.d_unit_panel, upanel.size() * 4));
-    SPMV_TRY(hipMalloc((void **)&p.d_panel_unit, punit.size() * 4));
-    SPMV_TRY(hipMemcpyAsync(p.d_unit_panel, upanel.data(), upanel.size() * 4, hipMemcpyHostToDevice, s));
-    SPMV_TRY(hipMemcpyAsync(p.d_panel_unit, punit.data(), punit.size() * 4, hipMemcpyHostToDevice, s));
-
+    const uint32_t S = (uint32_t)p.npanels;     // sort segments = the panels
+    const uint32_t *d_srow = p.d_panel_row;     // their rows
     // bucket shift so that S * buckets fits 32-bit keys
     uint32_t shift = 0;
     while ((uint64_t(S) * ((uint64_t(p.nr_cols) >> shift) + 1)) >= (1ull << 32))
@@ -1628,184 +1422,263 @@ int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src,
     int end_bit = 1;
     while (end_bit < 32 && (1ull << end_bit) < uint64_t(S) * nbuckets)
         ++end_bit;
-
-    SPMV_TRY(hipMalloc((void **)&p.d_panel_row, (P + 1) * 4));
-    SPMV_TRY(hipMalloc((void **)&p.d_unit_ent, uent.size() * 4));
-    SPMV_TRY(hipMemcpyAsync(p.d_panel_row, prow.data(), (P + 1) * 4, hipMemcpyHostToDevice, s));
-    uint32_t *d_srow = p.d_panel_row;  // rows of the sort segments (the panels)
-    SPMV_TRY(hipMemcpyAsync(p.d_unit_ent, uent.data(), uent.size() * 4, hipMemcpyHostToDevice, s));
-    SPMV_TRY(hipMalloc((void **)&p.d_s_col, std::max<uint64_t>(p.ent_pad, 4) * 4));
-    SPMV_TRY(hipMalloc((void **)&p.d_s_row, std::max<uint64_t>(p.ent_pad, 4) * 2));
-    SPMV_TRY(hipMalloc((void **)&p.d_s_val, std::max<uint64_t>(p.ent_pad, 4) * sizeof(ValueType)));
-
-    uint32_t *d_off = nullptr, *d_poff = nullptr;
-    IndexType *d_rp = nullptr;
-    uint32_t *k0 = nullptr, *k1 = nullptr, *i0 = nullptr, *i1 = nullptr;
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
-    uint8_t *d_wide = nullptr;     // per chunk: its columns span >= 65536 (side-table chunk)
-    uint32_t *d_abs = nullptr;     // a wide plan's absolute columns, lane-ordered
-    auto cleanup = [&]() {
-        for (void *q : {(void *)d_off, (void *)d_poff, (void *)d_rp, (void *)k0, (void *)k1, (void *)i0,
-                        (void *)i1, tmp, (void *)d_wide, (void *)d_abs})
-            if (q)
-                (void)hipFree(q);
-    };
-    auto fail = [&](hipError_t e, const char *what) {
-        set_error(std::string("build_sweep: ") + what + ": " + hipGetErrorString(e));
-        cleanup();
-        return 1;
-    };
-#define SW_TRY(x)                              \
-    do {                                       \
-        hipError_t e_ = (x);                   \
-        if (e_ != hipSuccess)                  \
-            return fail(e_, #x);               \
-    } while (0)
-    SW_TRY(hipMalloc((void **)&d_off, (S + 1) * 4));
-    SW_TRY(hipMalloc((void **)&d_poff, (S + 1) * 4));
-    SW_TRY(hipMalloc((void **)&d_rp, (size_t(n) + 1) * 4));
-    SW_TRY(hipMemcpyAsync(d_off, off.data(), (S + 1) * 4, hipMemcpyHostToDevice, s));
-    SW_TRY(hipMemcpyAsync(d_poff, poff.data(), (S + 1) * 4, hipMemcpyHostToDevice, s));
-    SW_TRY(hipMemcpyAsync(d_rp, h_rp, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
+    device_buf<uint32_t> d_off, d_poff, k0, k1, i0, i1;
+    device_buf<IndexType> d_rp;
+    device_buf<unsigned char> tmp;
+    SPMV_BUILD_TRY(d_off.alloc(S + 1));
+    SPMV_BUILD_TRY(d_poff.alloc(S + 1));
+    SPMV_BUILD_TRY(d_rp.alloc(size_t(n) + 1));
+    SPMV_BUILD_TRY(hipMemcpyAsync(d_off, u.off.data(), (S + 1) * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMemcpyAsync(d_poff, u.poff.data(), (S + 1) * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMemcpyAsync(d_rp, h_rp, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
     if (nnz) {
-        SW_TRY(hipMalloc((void **)&k0, nnz * 4));
-        SW_TRY(hipMalloc((void **)&k1, nnz * 4));
-        SW_TRY(hipMalloc((void **)&i0, nnz * 4));
-        SW_TRY(hipMalloc((void **)&i1, nnz * 4));
-        hipLaunchKernelGGL(k_sweep_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_rp, d_col_src,
-                           d_srow, S, n, nbuckets, shift, k0, i0);
-        SW_TRY(hipGetLastError());
+        SPMV_BUILD_TRY(k0.alloc(nnz));
+        SPMV_BUILD_TRY(k1.alloc(nnz));
+        SPMV_BUILD_TRY(i0.alloc(nnz));
+        SPMV_BUILD_TRY(i1.alloc(nnz));
+        SPMV_BUILD_TRY(launch_items(k_sweep_keys, n, 256, s, d_rp.get(), d_col_src, d_srow, S, n, nbuckets, shift,
+                                    k0.get(), i0.get()));
         // 64-bit item count: a slice may hold more than 2^31 non-zeros (up to the 32-bit padded
-        // layout checked above)
-        SW_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k0, k1, i0, i1, (uint64_t)nnz, 0, end_bit, s));
-        SW_TRY(hipMalloc(&tmp, tmp_bytes));
-        SW_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, k0, k1, i0, i1, (uint64_t)nnz, 0, end_bit, s));
-        hipLaunchKernelGGL((k_sweep_scatter<ValueType>), dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, k1,
-                           i1, nnz, nbuckets, d_rp, n, d_col_src, d_val_src, d_srow, d_off, d_poff,
-                           p.d_s_col, p.d_s_row, p.d_s_val);
-        SW_TRY(hipGetLastError());
+        // layout the planner checked)
+        size_t tmp_bytes = 0;
+        auto sort = [&](void *work) {
+            return hipcub::DeviceRadixSort::SortPairs(work, tmp_bytes, k0.get(), k1.get(), i0.get(), i1.get(), nnz, 0,
+                                                      end_bit, s);
+        };
+        SPMV_BUILD_TRY(sort(nullptr));
+        SPMV_BUILD_TRY(tmp.alloc(tmp_bytes));
+        SPMV_BUILD_TRY(sort(tmp.p));
+        SPMV_BUILD_TRY(launch_items(k_sweep_scatter<ValueType>, nnz, 256, s, k1.get(), i1.get(), nnz, nbuckets,
+                                    d_rp.get(), n, d_col_src, d_val_src, d_srow, d_off.get(), d_poff.get(), p.d_s_col,
+                                    p.d_s_row, p.d_s_val));
     }
-    hipLaunchKernelGGL((k_sweep_pad<ValueType>), dim3((S + 255) / 256), dim3(256), 0, s, S, d_srow, d_off,
-                       d_poff, p.d_s_col, p.d_s_row, p.d_s_val);
-    SW_TRY(hipGetLastError());
-    // 12-byte packed entries when every 128-entry chunk spans < 65536 columns
+    SPMV_BUILD_TRY(launch_items(k_sweep_pad<ValueType>, S, 256, s, S, d_srow, d_off.get(), d_poff.get(), p.d_s_col,
+                                p.d_s_row, p.d_s_val));
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));  // the scratch goes with the scope
+    return 0;
+}
+
+// Build step 2: the base column of every 128-entry chunk (p.d_s_cbase), which chunks span
+// >= 65536 columns (d_wide: side-table chunks) and how many do (*bad).
+static int sweep_chunk_bases(spmv_plan &p, hipStream_t s, device_buf<uint8_t> &d_wide, uint32_t *bad)
+{
+    const uint64_t nchunks = p.ent_pad / kSweepChunk;
+    device_buf<uint32_t> d_bad;
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_cbase, std::max<uint64_t>(nchunks, 1) * 4));
+    SPMV_BUILD_TRY(d_bad.alloc(1));
+    SPMV_BUILD_TRY(hipMemsetAsync(d_bad, 0, 4, s));
+    SPMV_BUILD_TRY(d_wide.alloc(std::max<uint64_t>(nchunks, 1)));
+    if (nchunks)
+        SPMV_BUILD_TRY(launch_items(k_sweep_chunk_base, nchunks, 256, s, p.d_s_col, nchunks, (uint32_t)kSweepChunk,
+                                    p.d_s_cbase, d_bad.get(), d_wide.get()));
+    *bad = 0;
+    SPMV_BUILD_TRY(hipMemcpyAsync(bad, d_bad, 4, hipMemcpyDeviceToHost, s));
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Build step 3: 12-byte packed entries (row and 16-bit column offset in one word; a wide plan's
+// absolute columns go to d_abs, lane-ordered, for the side table) and, with `lane`, every chunk
+// in lane order.
+static int sweep_pack(spmv_plan &p, hipStream_t s, bool wide, bool lane, const device_buf<uint8_t> &d_wide,
+                      device_buf<uint32_t> &d_abs)
+{
+    if (wide) {
+        SPMV_BUILD_TRY(d_abs.alloc(p.ent_pad));
+        SPMV_BUILD_TRY(launch_items(k_sweep_lane_order_u32, p.ent_pad, 256, s, p.d_s_col, p.ent_pad, d_abs.get()));
+        p.sweep_wide = true;
+    }
+    SPMV_BUILD_TRY(launch_items(k_sweep_pack_rc, p.ent_pad, 256, s, p.d_s_col, p.d_s_row, p.d_s_cbase, p.ent_pad, 7u,
+                                d_wide.get()));
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
+    SPMV_BUILD_TRY(hipFree(p.d_s_row));
+    p.d_s_row = nullptr;
+    p.sweep_packed = true;
+    if (!lane)
+        return 0;
+    device_buf<uint32_t> rc2;
+    device_buf<ValueType> v2;
+    SPMV_BUILD_TRY(rc2.alloc(p.ent_pad));
+    SPMV_BUILD_TRY(v2.alloc(p.ent_pad));
+    SPMV_BUILD_TRY(launch_items(k_sweep_lane_order<ValueType>, p.ent_pad, 256, s, p.d_s_col, p.d_s_val, p.ent_pad,
+                                rc2.get(), v2.get()));
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
+    rc2.swap(p.d_s_col);  // the plan takes the lane-ordered arrays; the CSR-ordered ones are
+    v2.swap(p.d_s_val);   // freed here, before the delta form allocates
+    SPMV_BUILD_TRY(rc2.release());
+    SPMV_BUILD_TRY(v2.release());
+    p.sweep_lane_order = true;
+    return 0;
+}
+
+// Build step 4: delta-coded columns for the default kernel, with the side table of the chunks
+// that have no 8-bit deltas (a gap > 511) or no 16-bit offsets (d_wide, columns from d_abs).
+static int sweep_delta_encode(spmv_plan &p, hipStream_t s, const device_buf<uint8_t> &d_wide,
+                              const device_buf<uint32_t> &d_abs)
+{
+    const uint64_t nchunks = p.ent_pad / kSweepChunk;
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_row16, p.ent_pad * 2));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_d8, p.ent_pad));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_dbase, nchunks * 4));
+    std::vector<uint8_t> hf(nchunks);
     {
-        const uint32_t group = kSweepChunk, gshift = 7;
-        const uint64_t nchunks = p.ent_pad / group;
-        SW_TRY(hipMalloc((void **)&p.d_s_cbase, std::max<uint64_t>(nchunks, 1) * 4));
-        uint32_t *d_bad = d_off;  // reuse: d_off is no longer needed once the scatter ran
-        SW_TRY(hipStreamSynchronize(s));
-        SW_TRY(hipMemsetAsync(d_bad, 0, 4, s));
-        SW_TRY(hipMalloc((void **)&d_wide, std::max<uint64_t>(nchunks, 1)));
-        if (nchunks)
-            hipLaunchKernelGGL(k_sweep_chunk_base, dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, s,
-                               p.d_s_col, nchunks, group, p.d_s_cbase, d_bad, d_wide);
-        SW_TRY(hipGetLastError());
-        uint32_t bad = 0;
-        SW_TRY(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
-        SW_TRY(hipStreamSynchronize(s));
-        const char *env = ablation_env("SPMV_SWEEP_PACKED");
-        const bool want = !(env && env[0] == '0');
-        const char *lo = ablation_env("SPMV_SWEEP_LANE_ORDER");
-        const bool lane = !(lo && lo[0] == '0');
-        // the delta-coded entries below (SPMV_SWEEP_DELTA=0 keeps the 12-byte words only).
-        // SPMV_SWEEP_DETERMINISTIC=1 plans keep the 12-byte words: the turn kernel on the 11-byte
-        // entries measured 0.897 vs 0.871 ms (its deeper pipeline has no room for the decode,
-        // profiles/r03_delta_columns.jsonl r03p)
-        const char *de = std::getenv("SPMV_SWEEP_DELTA");
-        const bool delta = lane && !(de && de[0] == '0') && !det && nchunks && uint64_t(p.nr_cols) < (1ull << 31) &&
-                           rmax_used < 32768;
-        // a chunk whose columns span >= 65536 has no 16-bit offsets: the delta form carries its
-        // absolute columns in the side table (a plan with a few such chunks -- panels of a few
-        // entries spread over the columns, e.g. beside a long run of empty rows -- reads only the
-        // 11-byte entries). Side chunks stream 15 B per entry, so when more than 1 chunk in 10 is
-        // wide (sparse panels throughout), or without the delta form, the plan keeps the
-        // unpacked 14-byte entries
-        if ((!bad || (delta && uint64_t(bad) * 10 <= nchunks)) && want && p.ent_pad) {
-            if (bad) {
-                SW_TRY(hipMalloc((void **)&d_abs, p.ent_pad * 4));
-                hipLaunchKernelGGL(k_sweep_lane_order_u32, dim3((unsigned)((p.ent_pad + 255) / 256)), dim3(256), 0, s,
-                                   p.d_s_col, p.ent_pad, d_abs);
-                SW_TRY(hipGetLastError());
-                p.sweep_wide = true;
-            }
-            hipLaunchKernelGGL(k_sweep_pack_rc, dim3((unsigned)((p.ent_pad + 255) / 256)), dim3(256), 0, s, p.d_s_col,
-                               p.d_s_row, p.d_s_cbase, p.ent_pad, gshift, d_wide);
-            SW_TRY(hipGetLastError());
-            SW_TRY(hipStreamSynchronize(s));
-            SW_TRY(hipFree(p.d_s_row));
-            p.d_s_row = nullptr;
-            p.sweep_packed = true;
-            if (lane) {
-                uint32_t *rc2 = nullptr;
-                ValueType *v2 = nullptr;
-                SW_TRY(hipMalloc((void **)&rc2, p.ent_pad * 4));
-                SW_TRY(hipMalloc((void **)&v2, p.ent_pad * sizeof(ValueType)));
-                hipLaunchKernelGGL((k_sweep_lane_order<ValueType>), dim3((unsigned)((p.ent_pad + 255) / 256)), dim3(256),
-                                   0, s, p.d_s_col, p.d_s_val, p.ent_pad, rc2, v2);
-                SW_TRY(hipGetLastError());
-                SW_TRY(hipStreamSynchronize(s));
-                SW_TRY(hipFree(p.d_s_col));
-                SW_TRY(hipFree(p.d_s_val));
-                p.d_s_col = rc2;
-                p.d_s_val = v2;
-                p.sweep_lane_order = true;
-                // delta-coded columns for the default kernel (conditions above)
-                if (delta) {
-                    uint8_t *d_flag = nullptr;
-                    uint32_t *d_sidx = nullptr;
-                    SW_TRY(hipMalloc((void **)&p.d_s_row16, p.ent_pad * 2));
-                    SW_TRY(hipMalloc((void **)&p.d_s_d8, p.ent_pad));
-                    SW_TRY(hipMalloc((void **)&p.d_s_dbase, nchunks * 4));
-                    SW_TRY(hipMalloc((void **)&d_flag, nchunks));
-                    hipLaunchKernelGGL((k_sweep_delta<ValueType>), dim3((unsigned)((nchunks + 63) / 64)), dim3(64), 0, s,
-                                       p.d_s_col, p.d_s_val, nchunks, p.d_s_row16, p.d_s_d8, d_flag, d_wide);
-                    hipError_t e = hipGetLastError();
-                    std::vector<uint8_t> hf(nchunks);
-                    if (e == hipSuccess)
-                        e = hipMemcpyAsync(hf.data(), d_flag, nchunks, hipMemcpyDeviceToHost, s);
-                    if (e == hipSuccess)
-                        e = hipStreamSynchronize(s);
-                    (void)hipFree(d_flag);
-                    SW_TRY(e);
-                    std::vector<uint32_t> sidx(nchunks, 0xFFFFFFFFu);
-                    uint64_t ns = 0;
-                    for (uint64_t c = 0; c < nchunks; ++c)
-                        if (hf[c])
-                            sidx[c] = (uint32_t)ns++;
-                    p.sweep_side_chunks = ns;
-                    SW_TRY(hipMalloc((void **)&p.d_s_side, std::max<uint64_t>(ns, 1) * kSweepChunk * 4));
-                    SW_TRY(hipMalloc((void **)&d_sidx, nchunks * 4));
-                    e = hipMemcpyAsync(d_sidx, sidx.data(), nchunks * 4, hipMemcpyHostToDevice, s);
-                    if (e == hipSuccess) {
-                        hipLaunchKernelGGL(k_sweep_delta_base, dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, s,
-                                           p.d_s_col, p.d_s_cbase, d_sidx, nchunks, p.d_s_dbase, p.d_s_side, d_wide,
-                                           d_abs);
-                        e = hipGetLastError();
-                    }
-                    if (e == hipSuccess)
-                        e = hipStreamSynchronize(s);
-                    (void)hipFree(d_sidx);
-                    SW_TRY(e);
-                    p.sweep_delta = true;
-                    // split plans can run the measurement build's work-stealing variants (the separate
-                    // combine kernel re-arms the counters)
-                    p.sweep_steal = p.sweep_split > 1 && p.d_steal && !p.d_panel_cnt;
-                    // the default kernel reads only the 11-byte entries: the rc words are freed
-                    // (rebuilt by sweep_materialize_rc for a variant that reads them)
-                    SW_TRY(hipFree(p.d_s_col));
-                    p.d_s_col = nullptr;
-                }
-            }
-        } else {
-            SW_TRY(hipFree(p.d_s_cbase));
-            p.d_s_cbase = nullptr;
+        device_buf<uint8_t> d_flag;
+        SPMV_BUILD_TRY(d_flag.alloc(nchunks));
+        SPMV_BUILD_TRY(launch_items(k_sweep_delta<ValueType>, nchunks, 64, s, p.d_s_col, p.d_s_val, nchunks, p.d_s_row16,
+                                    p.d_s_d8, d_flag.get(), d_wide.get()));
+        SPMV_BUILD_TRY(hipMemcpyAsync(hf.data(), d_flag, nchunks, hipMemcpyDeviceToHost, s));
+        SPMV_BUILD_TRY(hipStreamSynchronize(s));
+    }
+    std::vector<uint32_t> sidx(nchunks, 0xFFFFFFFFu);
+    uint64_t ns = 0;
+    for (uint64_t c = 0; c < nchunks; ++c)
+        if (hf[c])
+            sidx[c] = (uint32_t)ns++;
+    p.sweep_side_chunks = ns;
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_side, std::max<uint64_t>(ns, 1) * kSweepChunk * 4));
+    device_buf<uint32_t> d_sidx;
+    SPMV_BUILD_TRY(d_sidx.alloc(nchunks));
+    SPMV_BUILD_TRY(hipMemcpyAsync(d_sidx, sidx.data(), nchunks * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(launch_items(k_sweep_delta_base, nchunks, 256, s, p.d_s_col, p.d_s_cbase, d_sidx.get(), nchunks,
+                                p.d_s_dbase, p.d_s_side, d_wide.get(), d_abs.get()));
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
+    SPMV_BUILD_TRY(d_sidx.release());
+    p.sweep_delta = true;
+    // split plans can run the measurement build's work-stealing variants (the separate
+    // combine kernel re-arms the counters)
+    p.sweep_steal = p.sweep_split > 1 && p.d_steal && !p.d_panel_cnt;
+    // the default kernel reads only the 11-byte entries: the rc words are freed
+    // (rebuilt by sweep_materialize_rc for a variant that reads them)
+    SPMV_BUILD_TRY(hipFree(p.d_s_col));
+    p.d_s_col = nullptr;
+    return 0;
+}
+
+// The panels and work units come from the host planner (layout.cpp: plan_panels, plan_sweep_units);
+// this reads the switches, uploads the layout and encodes the entries in the four steps above.
+int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, const ValueType *d_val_src,
+                hipStream_t s)
+{
+    const IndexType n = p.nr_rows;
+    // a workgroup of T threads gets T/1024 of one CU's LDS for its panel's y
+    const uint64_t lds_bytes = kSweepLdsBytes * p.sweep_threads / 1024 - 256;  // 256 B: static LDS
+    // accumulator: fp64, or fp32 (compare-and-swap adds) for fp32 matrices with env SPMV_SWEEP_ACC=32
+    const char *aenv = ablation_env("SPMV_SWEEP_ACC");
+    p.sweep_acc_bytes = sizeof(ValueType) == 4 && aenv && std::atoi(aenv) == 32 ? 4 : 8;
+    const uint64_t acc = p.sweep_acc_bytes;
+    const uint32_t rmax = (uint32_t)std::min<uint64_t>(lds_bytes / acc - 1, 65534);
+    const int chip_cus = device_cu_count(p.device);
+    panel_options po;
+    po.wgs = (uint64_t)chip_cus * (1024 / p.sweep_threads);  // resident workgroups per round
+    // env SPMV_SWEEP_SPLIT: 0 = never split, 2 = split whenever >= 2 pieces fit, else heuristic
+    const char *senv = ablation_env("SPMV_SWEEP_SPLIT");
+    po.allow_split = !(senv && senv[0] == '0');
+    po.force_split = senv && senv[0] == '2';
+    po.acc_bytes = acc;
+    // env SPMV_SWEEP_DETERMINISTIC=1: the same layout, run by k_spmv_sweep_turn (ordered adds)
+    const char *denv = std::getenv("SPMV_SWEEP_DETERMINISTIC");
+    const bool det = denv && denv[0] == '1';
+    // XCC bias: the units the round-robin dispatch sends to even XCCs (unit % 8 even; block b
+    // runs on XCC b % 8 in every launch probed, tools/xcc_map_probe.py) get (1 - d) x the mean
+    // entries, the odd ones (1 + d) x; weight of the units [0, u): u - d * (u & 1). Why and the
+    // measurements: DESIGN.md §4 "XCC bias". Defaults on a whole chip (256 CUs = 8 XCDs): d = 0.015
+    // for whole panels, even split pieces (which XCCs sweep slower varies from box to box); env
+    // SPMV_SWEEP_XCC_BIAS=d overrides both (0 = even cut). The cut is a function of the matrix and
+    // the chip's CU count only, like the reference's (csr_hw.cpp:459-468).
+    const char *xbenv = std::getenv("SPMV_SWEEP_XCC_BIAS");
+    double xbias_split = xbenv ? std::atof(xbenv) : 0.0;
+    po.xbias = xbenv ? std::atof(xbenv) : chip_cus == 256 ? 0.015 : 0.0;
+    if (!(po.xbias > -0.5 && po.xbias < 0.5))
+        po.xbias = xbias_split = 0.0;
+    po.P_first = min_panels(n, rmax);
+    // (tools build) SPMV_SWEEP_ROUNDS=k: at least k rounds of whole panels on a matrix that fills
+    // a round anyway (smaller panels: earlier first panels for a streamed copy-back)
+    if (const char *ke = ablation_env("SPMV_SWEEP_ROUNDS"); ke && std::atoi(ke) > 0 && po.P_first * 2 >= po.wgs)
+        po.P_first = std::max<uint64_t>(po.P_first, (uint64_t)std::min(std::atoi(ke), 8) * po.wgs);
+    // env SPMV_SWEEP_PIECES=k (experiments): k pieces per panel in split mode instead of wgs / P
+    const char *kenv = ablation_env("SPMV_SWEEP_PIECES");
+    panel_cut cut;
+    sweep_units u;
+    if (int rc = plan_panels(kWho, h_rp, n, p.nnz, rmax, po, cut))
+        return rc;
+    if (int rc = plan_sweep_units(kWho, h_rp, cut.prow, cut.split_mode, po.wgs, kenv ? std::atoi(kenv) : 0,
+                                  xbias_split, u))
+        return rc;
+    const uint32_t P = (uint32_t)(cut.prow.size() - 1), U = u.punit[P];
+    p.npanels = P;
+    p.panel_rmax = u.rmax_used;
+    p.ent_pad = u.poff[P];
+    p.sweep_det = det;
+    p.xbias_split = u.xbias_split;
+    p.sweep_split = u.sweep_split;  // > 1: combine kernel needed
+    p.nunits = U;
+    if (u.sweep_split > 1) {
+        SPMV_BUILD_TRY(hipMalloc((void **)&p.d_part, (uint64_t)U * (uint64_t(u.rmax_used) + 1) * acc));
+#ifdef SPMV_ABLATIONS
+        // work-stealing counters of the measurement variants (zero; every k_sweep_combine re-arms them)
+        SPMV_BUILD_TRY(hipMalloc((void **)&p.d_steal, (uint64_t)U * 8));
+        SPMV_BUILD_TRY(hipMemsetAsync(p.d_steal, 0, (uint64_t)U * 8, s));
+#endif
+        // env SPMV_SWEEP_COMBINE=fused: the last piece of each panel combines inside the sweep
+        // launch instead of k_sweep_combine. Measured slower (0.147 vs 0.128 ms on the N = 8 slice of
+        // the 10M/160M matrix, profiles/r03_ab_sweep_combine.jsonl): each last arriver reads its
+        // partials alone where the combine kernel reads them with the whole chip
+        const char *cenv = ablation_env("SPMV_SWEEP_COMBINE");
+        if (cenv && std::strcmp(cenv, "fused") == 0) {
+            SPMV_BUILD_TRY(hipMalloc((void **)&p.d_panel_cnt, std::max<uint64_t>(P, 1) * 4));
+            SPMV_BUILD_TRY(hipMemsetAsync(p.d_panel_cnt, 0, std::max<uint64_t>(P, 1) * 4, s));
         }
     }
-    SW_TRY(hipStreamSynchronize(s));
-#undef SW_TRY
-    cleanup();
+    const uint64_t ents = std::max<uint64_t>(p.ent_pad, 4);
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_unit_panel, u.upanel.size() * 4));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_panel_unit, u.punit.size() * 4));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_panel_row, (P + 1) * 4));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_unit_ent, u.uent.size() * 4));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_unit_panel, u.upanel.data(), u.upanel.size() * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_panel_unit, u.punit.data(), u.punit.size() * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_panel_row, cut.prow.data(), (P + 1) * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_unit_ent, u.uent.data(), u.uent.size() * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_col, ents * 4));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_row, ents * 2));
+    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_val, ents * sizeof(ValueType)));
+
+    if (int rc = sweep_sort_entries(p, u, h_rp, d_col_src, d_val_src, s))
+        return rc;
+    device_buf<uint8_t> d_wide;   // per chunk: its columns span >= 65536 (side-table chunk)
+    device_buf<uint32_t> d_abs;   // a wide plan's absolute columns, lane-ordered
+    uint32_t bad = 0;
+    if (int rc = sweep_chunk_bases(p, s, d_wide, &bad))
+        return rc;
+    const uint64_t nchunks = p.ent_pad / kSweepChunk;
+    const char *env = ablation_env("SPMV_SWEEP_PACKED");
+    const bool want = !(env && env[0] == '0');
+    const char *lo = ablation_env("SPMV_SWEEP_LANE_ORDER");
+    const bool lane = !(lo && lo[0] == '0');
+    // the delta-coded entries (SPMV_SWEEP_DELTA=0 keeps the 12-byte words only).
+    // SPMV_SWEEP_DETERMINISTIC=1 plans keep the 12-byte words: the turn kernel on the 11-byte
+    // entries measured 0.897 vs 0.871 ms (its deeper pipeline has no room for the decode,
+    // profiles/r03_delta_columns.jsonl r03p)
+    const char *de = std::getenv("SPMV_SWEEP_DELTA");
+    const bool delta = lane && !(de && de[0] == '0') && !det && nchunks && uint64_t(p.nr_cols) < (1ull << 31) &&
+                       u.rmax_used < 32768;
+    // 12-byte packed entries when every 128-entry chunk spans < 65536 columns.
+    // a chunk whose columns span >= 65536 has no 16-bit offsets: the delta form carries its
+    // absolute columns in the side table (a plan with a few such chunks -- panels of a few
+    // entries spread over the columns, e.g. beside a long run of empty rows -- reads only the
+    // 11-byte entries). Side chunks stream 15 B per entry, so when more than 1 chunk in 10 is
+    // wide (sparse panels throughout), or without the delta form, the plan keeps the
+    // unpacked 14-byte entries
+    if ((!bad || (delta && uint64_t(bad) * 10 <= nchunks)) && want && p.ent_pad) {
+        if (int rc = sweep_pack(p, s, bad != 0, lane, d_wide, d_abs))
+            return rc;
+        if (delta)
+            if (int rc = sweep_delta_encode(p, s, d_wide, d_abs))
+                return rc;
+    } else {
+        SPMV_BUILD_TRY(hipFree(p.d_s_cbase));
+        p.d_s_cbase = nullptr;
+    }
+    SPMV_BUILD_TRY(hipStreamSynchronize(s));
     return 0;
 }
 

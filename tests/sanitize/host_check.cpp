@@ -1,12 +1,15 @@
 // Host-only check program for the sanitizer builds (tests/sanitize/Makefile): drives the host
 // code of libspmv_hw -- the multi-threaded reader (reader.cpp), the row partition, the exchange
-// schedule, the threaded accum_results '+=' (host.cpp), verification and storage_overhead --
+// schedule, the threaded accum_results '+=' (host.cpp), the layout planner (layout.cpp), verification
+// and storage_overhead --
 // compiled with g++ under AddressSanitizer + UBSan and under ThreadSanitizer. No HIP.
 //
 //   host_check read <file.mtx> <out.bin>   spmv_read_csr -> binary dump (n, m, nnz, row_ptr, col, val)
 //                                          and the header/matrix pair of calls, compared
 //   host_check partition                   random row_ptr, 1..16 units, against a restated S1 rule
 //   host_check slice                       slice_from_host on whole, empty, last-row and random ranges
+//   host_check layout                      the sweep / binned layout planner (layout.cpp): invariants of
+//                                          panels, units, windows and segments; pinned edge cases
 //   host_check schedule                    every exchange at 1..8 ranks, rows covered once
 //   host_check accumulate                  producer threads land parts while 16 threads add them
 //   host_check verify                      verification / storage_overhead semantics
@@ -234,6 +237,224 @@ static int cmd_slice()
     return 0;
 }
 
+// ---- the layout planner (layout.cpp): invariants of its results, restated here, not its code ----
+
+static std::vector<IndexType> row_ptr_of(const std::vector<uint32_t> &len)
+{
+    std::vector<IndexType> rp(len.size() + 1, 0);
+    for (size_t i = 0; i < len.size(); ++i)
+        rp[i + 1] = rp[i] + len[i];
+    return rp;
+}
+
+// what every panel cut must satisfy; even_cut: also the restated nnz-balanced rule (the caller
+// knows that the cut is unbiased and that the search cannot have subdivided)
+static void check_panels(const std::vector<IndexType> &rp, uint32_t rmax, const panel_options &o, const panel_cut &c,
+                         bool even_cut)
+{
+    const IndexType n = IndexType(rp.size() - 1);
+    const uint64_t nnz = rp[n], P = c.prow.size() - 1;
+    CHECK(c.prow.size() >= 2 && c.prow[0] == 0 && c.prow.back() == n);
+    for (uint64_t q = 0; q < P; ++q) {
+        CHECK(c.prow[q + 1] >= c.prow[q]);
+        CHECK(c.prow[q + 1] - c.prow[q] <= rmax);
+    }
+    CHECK(o.allow_split || !c.split_mode);
+    if (!even_cut)
+        return;
+    if (!c.split_mode && P > 1)
+        CHECK(P % o.wgs == 0 || P == n);  // whole rounds of workgroups
+    uint32_t want = 0;
+    for (uint64_t q = 1; q < P; ++q) {  // the first row whose start reaches q/P of the entries
+        const uint64_t target = nnz * q / P;
+        while (want < n && rp[want] < target)
+            ++want;
+        CHECK(c.prow[q] == want);
+    }
+}
+
+static void check_units(const std::vector<IndexType> &rp, const panel_cut &c, const sweep_units &u)
+{
+    const uint32_t P = uint32_t(c.prow.size() - 1);
+    CHECK(u.off.size() == P + 1u && u.poff.size() == P + 1u && u.punit.size() == P + 1u);
+    CHECK(u.off[0] == 0 && u.poff[0] == 0 && u.punit[0] == 0);
+    const uint32_t U = u.punit[P];
+    CHECK(u.uent.size() == U + 1u && u.upanel.size() == std::max<uint32_t>(U, 1));
+    uint32_t rows = 0;
+    bool multi = false;
+    for (uint32_t q = 0; q < P; ++q) {
+        const uint64_t cnt = uint64_t(rp[c.prow[q + 1]]) - rp[c.prow[q]];
+        CHECK(u.off[q] == rp[c.prow[q]] && u.off[q + 1] - u.off[q] == cnt);
+        CHECK(u.poff[q + 1] - u.poff[q] == (cnt + 127) / 128 * 128);
+        const uint64_t chunks = (u.poff[q + 1] - u.poff[q]) / 128, k = u.punit[q + 1] - u.punit[q];
+        CHECK(u.punit[q + 1] > u.punit[q]);  // at least one unit (also for a panel without entries)
+        CHECK(k <= std::max<uint64_t>(chunks, 1));
+        CHECK(u.uent[u.punit[q]] == u.poff[q]);
+        for (uint32_t t = u.punit[q]; t < u.punit[q + 1]; ++t)
+            CHECK(u.upanel[t] == q);
+        rows = std::max(rows, c.prow[q + 1] - c.prow[q]);
+        multi |= k > 1;
+    }
+    CHECK(u.uent[U] == u.poff[P] && u.rmax_used == rows);
+    for (uint32_t t = 0; t < U; ++t)
+        CHECK(u.uent[t + 1] >= u.uent[t] && u.uent[t] % 128 == 0);
+    CHECK((u.sweep_split > 1) == multi);
+    CHECK(c.split_mode || u.xbias_split == 0.0);
+}
+
+static void check_windows(uint64_t ncols, uint64_t cus, double d)
+{
+    const bin_windows w = plan_bin_windows(ncols, cus, d);
+    CHECK(w.nwin >= 1 && w.W0 + w.W1 == 2 * w.W);
+    for (uint64_t x : {w.W, w.W0, w.W1})
+        CHECK(x >= kBinPer && x <= w.wmax && x % kBinPer == 0);
+    CHECK(d != 0.0 || w.W0 == w.W1);
+    if (!ncols)
+        return;
+    // even windows W0 wide, odd ones W1: the last one starts inside [0, ncols) and ends at or past it
+    auto start = [&](uint64_t k) { return k / 2 * (w.W0 + w.W1) + (k & 1 ? w.W0 : 0); };
+    CHECK(start(w.nwin - 1) < ncols && start(w.nwin) >= ncols);
+}
+
+static void check_bin_units(const std::vector<uint32_t> &cnt, const std::vector<uint32_t> &esc, uint64_t nwin, uint64_t P,
+                            uint64_t cus)
+{
+    bin_units b;
+    plan_bin_units(cnt, esc, nwin, P, cus, b);
+    const uint64_t nseg = nwin * P;
+    CHECK(b.seg.size() == nseg + 1 && b.seg[0] == 0 && b.ub.size() == b.uwin.size() + 1);
+    for (uint64_t k = 0; k < nseg; ++k) {
+        CHECK(b.seg[k + 1] >= b.seg[k] + cnt[k] + esc[k]);  // monotone, and room for the segment
+        CHECK(b.seg[k + 1] % kBinPer == 0);
+    }
+    for (uint64_t w = 0; w <= nwin; ++w)
+        CHECK(b.seg[w * P] % kBinAlign == 0);
+    // the units of every non-empty window, in window order, tile the window's range once
+    size_t u = 0;
+    for (uint64_t w = 0; w < nwin; ++w) {
+        const uint64_t a = b.seg[w * P], e = b.seg[(w + 1) * P];
+        if (a == e)
+            continue;
+        CHECK(u < b.uwin.size() && b.uwin[u] == w && b.ub[u] == a);
+        for (; u < b.uwin.size() && b.uwin[u] == w; ++u)
+            CHECK(b.ub[u + 1] >= b.ub[u] && b.ub[u + 1] <= e && b.ub[u] % kBinAlign == 0);
+        CHECK(b.ub[u] == e);  // also the next non-empty window's start: empty ones take no room
+    }
+    CHECK(u == b.uwin.size());
+}
+
+// sweep (bias, split options) and binned (its first P, no split, no bias) on one row_ptr
+static void check_layout(const std::vector<IndexType> &rp, uint32_t rmax, uint64_t wgs, double bias, int split,
+                         int pieces, bool no_subdivide)
+{
+    const IndexType n = IndexType(rp.size() - 1);
+    const uint64_t nnz = rp[n];
+    panel_options o;
+    o.wgs = wgs;
+    o.P_first = min_panels(n, rmax);
+    o.allow_split = split != 0;
+    o.force_split = split == 2;
+    o.xbias = bias;
+    panel_cut c;
+    set_error("");
+    CHECK(plan_panels("sweep", rp.data(), n, nnz, rmax, o, c) == 0);  // "cannot form panels": never
+    CHECK(bias != 0.0 || c.xbias == 0.0);
+    check_panels(rp, rmax, o, c, no_subdivide && (c.split_mode || c.xbias == 0.0));
+    sweep_units u;
+    CHECK(plan_sweep_units("sweep", rp.data(), c.prow, c.split_mode, wgs, pieces, bias, u) == 0);
+    check_units(rp, c, u);
+    panel_options b;
+    b.wgs = wgs;
+    b.P_first = std::max<uint64_t>(min_panels(n, rmax), std::min<uint64_t>(wgs, n));
+    panel_cut cb;
+    CHECK(plan_panels("binned", rp.data(), n, nnz, rmax, b, cb) == 0);
+    check_panels(rp, rmax, b, cb, no_subdivide);
+    CHECK(!std::strlen(get_error()));
+}
+
+static int cmd_layout()
+{
+    std::mt19937_64 g(17);
+    const uint64_t wgss[] = {64, 256, 304};
+    const double biases[] = {0.0, 0.015, -0.02, 0.1, 0.49};
+    for (int it = 0; it < 400; ++it) {
+        // rows of 1..4 entries and rmax = 64: a panel cut at P holds fewer than nnz / P + 5 rows,
+        // so the search ends by P = 4 n / 59 -- inside its bound of 8 max(n / 64, wgs) and below
+        // P = n -- and never subdivides; the even cut's restated rule then holds
+        const bool plain = it % 2 == 0;
+        std::vector<uint32_t> len(it % 25 == 0 ? g() % 3 : g() % 4000);
+        for (auto &l : len)
+            l = plain ? 1 + uint32_t(g() % 4) : g() % 9 == 0 ? uint32_t(g() % 3000) : uint32_t(g() % 40 == 0 ? g() % 6 : 0);
+        const std::vector<IndexType> rp = row_ptr_of(len);
+        for (int k = 0; k < 3; ++k)
+            check_layout(rp, plain ? 64 : (g() % 2 ? 7 : 300), wgss[g() % 3], biases[g() % 5], int(g() % 3),
+                         g() % 2 ? 8 : 0, plain);
+    }
+    // pinned edge cases
+    for (uint64_t wgs : wgss)
+        for (double bias : {0.0, 0.1})
+            for (int split = 0; split < 3; ++split) {
+                check_layout({0}, 64, wgs, bias, split, 0, true);                               // n = 0
+                check_layout(std::vector<IndexType>(3001, 0), 64, wgs, bias, split, 0, false);  // nnz = 0
+                check_layout({0, 0}, 64, wgs, bias, split, 0, true);                            // n = 1
+                check_layout({0, 9}, 64, wgs, bias, split, 0, true);
+                std::vector<uint32_t> one(3000, 0);  // all entries in one row
+                one[1234] = 70000;
+                check_layout(row_ptr_of(one), 64, wgs, bias, split, 8, false);
+                // a trailing and a middle run of empty rows longer than rmax: subdivided, and
+                // (check_panels) no panel above rmax rows
+                std::vector<uint32_t> trail(3000, 0), mid(3000, 3);
+                std::fill(trail.begin(), trail.begin() + 1000, 3u);
+                std::fill(mid.begin() + 1000, mid.begin() + 2500, 0u);
+                check_layout(row_ptr_of(trail), 64, wgs, bias, split, 0, false);
+                check_layout(row_ptr_of(mid), 64, wgs, bias, split, 0, false);
+            }
+    {
+        // a bias on panels already at the row cap: the cut falls back to the even one
+        const std::vector<IndexType> rp = row_ptr_of(std::vector<uint32_t>(64 * 64, 5));
+        panel_options o;
+        o.wgs = 64;
+        o.P_first = min_panels(64 * 64, 64);
+        panel_cut even, biased;
+        CHECK(plan_panels("sweep", rp.data(), 64 * 64, rp.back(), 64, o, even) == 0);
+        o.xbias = 0.1;
+        CHECK(plan_panels("sweep", rp.data(), 64 * 64, rp.back(), 64, o, biased) == 0);
+        CHECK(even.prow.size() == 65 && biased.prow == even.prow && biased.xbias == 0.0 && !biased.split_mode);
+    }
+    {
+        // one row of 2^32 - 1 entries pads past 32 bits: rc 2
+        const std::vector<IndexType> rp = {0, 0xFFFFFFFFu};
+        panel_options o;
+        o.allow_split = true;
+        panel_cut c;
+        sweep_units u;
+        CHECK(plan_panels("build_sweep", rp.data(), 1, rp[1], 64, o, c) == 0);
+        CHECK(plan_sweep_units("build_sweep", rp.data(), c.prow, c.split_mode, o.wgs, 0, 0.0, u) == 2);
+        CHECK(!std::strcmp(get_error(), "build_sweep: padded entry count exceeds 32 bits"));
+    }
+    // binned: windows and segments
+    for (int it = 0; it < 3000; ++it) {
+        const uint64_t ncols = it < 64 ? uint64_t(it) : it % 3 ? g() % 200000 : g() % 60000000;
+        const double bb[] = {0.0, 0.05, -0.05, 0.2, -0.24, 0.3};
+        check_windows(ncols, wgss[g() % 3], bb[g() % 6]);
+    }
+    for (int it = 0; it < 300; ++it) {
+        const uint64_t nwin = 1 + g() % 400, P = 1 + g() % 40, cus = wgss[g() % 3];
+        std::vector<uint32_t> cnt(nwin * P), esc(nwin * P, 0);
+        const int mode = it % 4;  // 0: nothing at all; 3: whole windows empty
+        const uint64_t hole = g() % nwin;
+        for (uint64_t k = 0; k < nwin * P; ++k) {
+            cnt[k] = mode == 0 || (mode == 3 && (k / P) % 3 == hole % 3) ? 0 : g() % 4 ? uint32_t(g() % 300) : 0;
+            if (mode == 2 && g() % 60 == 0)
+                cnt[k] = uint32_t(g() % 200000);  // a heavy window
+            esc[k] = mode >= 2 && cnt[k] ? uint32_t(g() % 3) : 0;
+        }
+        check_bin_units(cnt, esc, nwin, P, cus);
+    }
+    std::printf("OK layout\n");
+    return 0;
+}
+
 static int cmd_schedule()
 {
     std::mt19937_64 g(9);
@@ -393,12 +614,14 @@ int main(int argc, char **argv)
         return cmd_partition();
     if (argc >= 2 && !std::strcmp(argv[1], "slice"))
         return cmd_slice();
+    if (argc >= 2 && !std::strcmp(argv[1], "layout"))
+        return cmd_layout();
     if (argc >= 2 && !std::strcmp(argv[1], "schedule"))
         return cmd_schedule();
     if (argc >= 2 && !std::strcmp(argv[1], "accumulate"))
         return cmd_accumulate();
     if (argc >= 2 && !std::strcmp(argv[1], "verify"))
         return cmd_verify();
-    std::fprintf(stderr, "usage: host_check read <mtx> <out> | partition | slice | schedule | accumulate | verify\n");
+    std::fprintf(stderr, "usage: host_check read <mtx> <out> | partition | slice | layout | schedule | accumulate | verify\n");
     return 2;
 }

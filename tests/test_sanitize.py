@@ -1,6 +1,7 @@
 """Sanitizer builds of the library's host code (SURVEY §5 "ASan/UBSan host build"; VERDICT r3
 item 3). tests/sanitize/Makefile compiles host.cpp (row partition, exchange schedule, threaded
-accum_results '+=', verification, storage_overhead) and reader.cpp (the 16-thread mmap reader)
+accum_results '+=', verification, storage_overhead), layout.cpp (the sweep / binned layout
+planner) and reader.cpp (the 16-thread mmap reader)
 with g++ -fsanitize=address,undefined (fp64 and fp32) and -fsanitize=thread into host_check, a
 small driver (tests/sanitize/host_check.cpp). This suite builds them and runs:
 
@@ -56,7 +57,7 @@ def _run(binary, *args, threads=None, timeout=300):
 
 
 @pytest.mark.parametrize("kind", list(BINS))
-@pytest.mark.parametrize("cmd", ["partition", "slice", "schedule", "accumulate", "verify"])
+@pytest.mark.parametrize("cmd", ["partition", "slice", "layout", "schedule", "accumulate", "verify"])
 def test_host_checks_clean_under_sanitizer(built, kind, cmd):
     p = _run(built[kind], cmd)
     assert p.returncode == 0, p.stdout + p.stderr
