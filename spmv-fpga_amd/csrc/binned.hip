@@ -830,6 +830,65 @@ int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
     return 0;
 }
 
+// ---- the binned row of the layout table (spmv_internal.hpp layout_ops) ----
+static uint64_t binned_device_bytes(const spmv_plan &p)  // entries (value, 2 offsets), products, segments, units, panels
+{
+    return p.ent_pad * (2 * sizeof(ValueType) + 2 + (p.b_delta ? 1 : 2)) + (uint64_t(p.b_nwin) * p.npanels + 1) * 8 +
+           (p.b_nunits + 1) * 12 + (p.npanels + 1) * 4;
+}
+
+static int binned_set_variant(spmv_plan &p, int variant)
+{
+    // 1 / 2 (tests, same y): pass 2 reads segment offsets rebased so that they straddle 2^31 /
+    // 2^32 entries (prod and rowp rebased the other way: the same addresses), which drives the
+    // 64-bit bound widening after readlane (k_bin_acc) without a 2^31-entry matrix
+    // 3-6 (same y): pass-1 cache policy (3: temporal product stores, 4: temporal entry
+    // loads, 5: both, 6: non-temporal stores; 0 = the plan's choice); 7 (same y): mirrored
+    // products (stored down the array while the entries stream up it); 51 / 52 (tools
+    // library): pass-2 ablations
+    if (variant > 7 && !(variant >= 51 && variant <= 52)) {
+        set_error("spmv_plan_set_variant: binned variants are 0-7");
+        return 1;
+    }
+    if (p.d_b_seg_hi) {
+        SPMV_TRY(hipSetDevice(p.device));
+        SPMV_TRY(hipFree(p.d_b_seg_hi));
+        p.d_b_seg_hi = nullptr;
+        p.b_seg_base = 0;
+    }
+    if (variant == 1 || variant == 2) {
+        SPMV_TRY(hipSetDevice(p.device));
+        const uint64_t nseg = uint64_t(p.b_nwin) * p.npanels + 1;
+        std::vector<uint64_t> h(nseg);
+        SPMV_TRY(hipMemcpy(h.data(), p.d_b_seg, nseg * 8, hipMemcpyDeviceToHost));
+        const uint64_t base = (variant == 1 ? (1ull << 31) : (1ull << 32)) - h[nseg - 1] / 2;
+        for (auto &v : h)
+            v += base;
+        SPMV_TRY(hipMalloc((void **)&p.d_b_seg_hi, nseg * 8));
+        SPMV_TRY(hipMemcpy(p.d_b_seg_hi, h.data(), nseg * 8, hipMemcpyHostToDevice));
+        p.b_seg_base = base;
+    }
+    p.variant = variant;
+    return 0;
+}
+
+const layout_ops &binned_layout()
+{
+    static const layout_ops row = {
+        "binned", "build binned layout", build_binned, kKernelSweep,  // (the segment table is too large, or skew)
+        nullptr, launch_of<launch_binned>, nullptr, warm_of<launch_binned>,
+        binned_device_bytes,
+        [](const spmv_plan &p) -> uint64_t { return p.npanels; },                              // units
+        [](const spmv_plan &p) -> uint64_t { return p.npanels ? p.ent_pad / p.npanels : 0; },  // unit_nnz
+        one_block,
+        [](const spmv_plan &p) -> int { return p.b_delta ? 32 : 0; },  // format_bits
+        [](const spmv_plan &p) -> uint64_t { return p.ent_pad; },      // stored_entries
+        [](const spmv_plan &p) -> void * { return p.d_b_colw; },       // index_stream
+        3, {1, 2}, binned_set_variant, false,  // tune_slot, product_variants, set_variant, host_y
+    };
+    return row;
+}
+
 }  // namespace spmvhw
 
 #ifdef SPMV_ABLATIONS

@@ -335,6 +335,8 @@ __global__ void k_blk_take(const uint32_t *__restrict__ src, const uint32_t *__r
 int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, const ValueType *d_val_src,
                   hipStream_t s)
 {
+    if (fpga_params(p))
+        return 1;
     const IndexType n = p.nr_rows;
     const uint64_t nnz = p.nnz;
     const uint32_t W = p.fpga_width;
@@ -548,6 +550,30 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
     BK_TRY(hipStreamSynchronize(s));
 #undef BK_TRY
     return 0;
+}
+
+// ---- the blocked row of the layout table (spmv_internal.hpp layout_ops) ----
+static uint64_t blocked_device_bytes(const spmv_plan &p)  // entries, kptr, kpos, rl, partials, rp2, chunks, units
+{
+    return p.nnz * (2 + sizeof(ValueType)) + (p.nkpairs + 1) * 4 + p.nkpairs * (4 + 2 + sizeof(ValueType)) +
+           (uint64_t(p.nr_rows) + 1) * 4 + (p.nchunks + 1) * 4 + p.nunits * 8 + 4;
+}
+
+const layout_ops &blocked_layout()
+{
+    static const layout_ops row = {
+        "blocked", "build CSR layout", build_blocked, -1,
+        nullptr, launch_of<launch_blocked>, nullptr, warm_of<launch_blocked>,
+        blocked_device_bytes,
+        [](const spmv_plan &p) -> uint64_t { return p.nunits; },                         // units
+        [](const spmv_plan &p) -> uint64_t { return p.nunits ? p.nnz / p.nunits : 0; },  // unit_nnz
+        [](const spmv_plan &p) -> uint32_t { return (uint32_t)((uint64_t(p.nr_cols) + p.fpga_width - 1) / p.fpga_width); },
+        [](const spmv_plan &) -> int { return 0; },               // format_bits
+        [](const spmv_plan &p) -> uint64_t { return p.nnz; },     // stored_entries
+        [](const spmv_plan &p) -> void * { return p.d_colnar; },  // index_stream
+        -1, {0, 0}, set_tile_variant, false,  // tune_slot, product_variants, set_variant, host_y
+    };
+    return row;
 }
 
 }  // namespace spmvhw

@@ -243,8 +243,8 @@ void setup_streaming(hw_matrix_impl *m)
     if (!m->copy_stream)  // (else made by create_csr_hw_matrix while the plan built)
         check(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking), "hipStreamCreate");
     const uint64_t rows = m->row_end - m->row_begin;
-    if (ablation_env("SPMV_HW_DIRECT") && pl.kernel == kKernelSweep) {  // the measurement form: y straight
-                                                                         // into host memory (sweep only)
+    if (ablation_env("SPMV_HW_DIRECT") && layout_of(pl.kernel).host_y) {  // the measurement form: y straight
+                                                                           // into host memory (sweep only)
         check(hipHostMalloc((void **)&m->h_direct, rows * sizeof(ValueType), hipHostMallocCoherent | hipHostMallocMapped),
               "hipHostMalloc(direct y)");
         check(hipHostGetDevicePointer((void **)&m->d_direct, m->h_direct, 0), "hipHostGetDevicePointer(direct y)");
@@ -718,22 +718,13 @@ void create_csr_hw_matrix(csr_matrix *matrix, csr_hw_matrix ***hw_matrix, bool *
         spmv_plan_stats st;
         spmv_plan_get_stats(h->plan, &st);
         const spmv_plan &pl = *h->plan;
-        const bool sweep = pl.kernel == kKernelSweep || pl.kernel == kKernelBinned;
-        const bool slices = pl.kernel == kKernelSlices;
+        const layout_ops &layout = layout_of(pl.kernel);
         // stored entries of the representation (padded for tiles, sweep and slices, plain for
         // gold / FPGA order / blocked)
-        const uint64_t stored = sweep    ? pl.ent_pad
-                                : slices ? pl.slice_slots * kWave
-                                : pl.kernel != kKernelTiles ? pl.nnz
-                                                            : pl.nnz_pad;
+        const uint64_t stored = layout.stored_entries(pl);
         const uint64_t val_bytes = stored * sizeof(ValueType);
         // the index stream of the unit's representation (opaque device address)
-        h->sub[0] = pl.kernel == kKernelBinned ? reinterpret_cast<BusDataType *>(pl.d_b_colw)
-                    : sweep ? (pl.d_s_col ? reinterpret_cast<BusDataType *>(pl.d_s_col)
-                                          : reinterpret_cast<BusDataType *>(pl.d_s_row16))
-                    : (slices || pl.kernel == kKernelBlocked || pl.tile_col_bytes < 4)
-                        ? reinterpret_cast<BusDataType *>(pl.d_colnar)
-                        : reinterpret_cast<BusDataType *>(pl.d_col);
+        h->sub[0] = static_cast<BusDataType *>(layout.index_stream(pl));
         h->nr_rows[0] = (IndexType)st.nr_nonempty_rows;
         h->nr_cols[0] = matrix->nr_cols;
         h->nr_nzeros[0] = (IndexType)stored;

@@ -179,4 +179,130 @@ hipError_t launch_gold(const spmv_plan &p, const ValueType *d_x, ValueType *d_y,
     return hipGetLastError();
 }
 
+// Gold-order representation (kernel 1): the CSR itself (nlong counts the rows longer than
+// kGoldLong, for the stats only).
+static int build_gold(spmv_plan &p, const IndexType *h_row_ptr, const IndexType *d_col_src,
+                      const ValueType *d_val_src, hipStream_t s)
+{
+    p.nlong = 0;
+    for (IndexType r = 0; r < p.nr_rows; ++r)
+        p.nlong += h_row_ptr[r + 1] - h_row_ptr[r] > (IndexType)kGoldLong;
+    SPMV_TRY(hipMalloc((void **)&p.d_rp, (size_t(p.nr_rows) + 1) * sizeof(uint32_t)));
+    SPMV_TRY(hipMalloc((void **)&p.d_col, std::max<uint64_t>(p.nnz, 1) * sizeof(uint32_t)));
+    SPMV_TRY(hipMalloc((void **)&p.d_val, std::max<uint64_t>(p.nnz, 1) * sizeof(ValueType)));
+    SPMV_TRY(hipMemcpyAsync(p.d_rp, h_row_ptr, (size_t(p.nr_rows) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (p.nnz) {
+        SPMV_TRY(hipMemcpyAsync(p.d_col, d_col_src, p.nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        SPMV_TRY(hipMemcpyAsync(p.d_val, d_val_src, p.nnz * sizeof(ValueType), hipMemcpyDeviceToDevice, s));
+    }
+    SPMV_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+// FPGA order: VF / block width from the environment (the reference's compile-time VF and
+// COLS_DIV_BLOCKS, util.h:31-59; defaults VF = 1 as its Makefile:16, 32768 columns), and every
+// row's entries stably ordered by column block (the reference walks each block's entries of a
+// row in CSR order, create_block_matrix); rows that are already block-ordered stay as they are.
+int fpga_params(spmv_plan &p)
+{
+    if (const char *v = std::getenv("SPMV_FPGA_VF")) {
+        const int vf = std::atoi(v);
+        if (vf != 1 && vf != 2 && vf != 4 && vf != 8) {
+            set_error("SPMV_FPGA_VF must be 1, 2, 4 or 8");
+            return 1;
+        }
+        p.fpga_vf = vf;
+    }
+    if (const char *b = std::getenv("SPMV_FPGA_BLOCK")) {
+        const long w = std::atol(b);
+        if (w < 1 || w > 0x7FFFFFFFL) {
+            set_error("SPMV_FPGA_BLOCK must be a positive column count");
+            return 1;
+        }
+        p.fpga_width = (uint32_t)w;
+    }
+    return 0;
+}
+
+static int order_rows_by_block(spmv_plan &p, const IndexType *h_row_ptr, hipStream_t s)
+{
+    if (fpga_params(p))
+        return 1;
+    if (!p.nnz)
+        return 0;
+    std::vector<uint32_t> col(p.nnz);
+    SPMV_TRY(hipMemcpyAsync(col.data(), p.d_col, p.nnz * 4, hipMemcpyDeviceToHost, s));
+    SPMV_TRY(hipStreamSynchronize(s));
+    bool sorted = true;
+    for (IndexType r = 0; r < p.nr_rows && sorted; ++r)
+        for (uint64_t k = uint64_t(h_row_ptr[r]) + 1; k < h_row_ptr[r + 1]; ++k)
+            if (col[k] / p.fpga_width < col[k - 1] / p.fpga_width) {
+                sorted = false;
+                break;
+            }
+    if (sorted)
+        return 0;
+    std::vector<ValueType> val(p.nnz);
+    SPMV_TRY(hipMemcpyAsync(val.data(), p.d_val, p.nnz * sizeof(ValueType), hipMemcpyDeviceToHost, s));
+    SPMV_TRY(hipStreamSynchronize(s));
+    std::vector<uint32_t> idx;
+    std::vector<uint32_t> c2(col);
+    std::vector<ValueType> v2(val);
+    for (IndexType r = 0; r < p.nr_rows; ++r) {
+        const uint64_t b = h_row_ptr[r], e = h_row_ptr[r + 1];
+        idx.resize(e - b);
+        for (uint64_t k = b; k < e; ++k)
+            idx[k - b] = (uint32_t)k;
+        std::stable_sort(idx.begin(), idx.end(),
+                         [&](uint32_t i, uint32_t j) { return col[i] / p.fpga_width < col[j] / p.fpga_width; });
+        for (uint64_t k = b; k < e; ++k) {
+            c2[k] = col[idx[k - b]];
+            v2[k] = val[idx[k - b]];
+        }
+    }
+    SPMV_TRY(hipMemcpyAsync(p.d_col, c2.data(), p.nnz * 4, hipMemcpyHostToDevice, s));
+    SPMV_TRY(hipMemcpyAsync(p.d_val, v2.data(), p.nnz * sizeof(ValueType), hipMemcpyHostToDevice, s));
+    SPMV_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+static int build_fpga(spmv_plan &p, const IndexType *h_row_ptr, const IndexType *d_col_src, const ValueType *d_val_src,
+                      hipStream_t s)
+{
+    return build_gold(p, h_row_ptr, d_col_src, d_val_src, s) || order_rows_by_block(p, h_row_ptr, s);
+}
+
+// ---- the gold and fpga rows of the layout table (spmv_internal.hpp layout_ops): the same CSR
+// layout, the stats' units are the long rows ----
+static uint64_t csr_device_bytes(const spmv_plan &p)
+{
+    return (uint64_t(p.nr_rows) + 1) * 4 + p.nnz * (4 + sizeof(ValueType));
+}
+
+static layout_ops csr_row(const char *name, decltype(layout_ops::build) build)
+{
+    return {
+        name, "build CSR layout", build, -1,
+        nullptr, launch_of<launch_gold>, nullptr, warm_of<launch_gold>,
+        csr_device_bytes,
+        [](const spmv_plan &p) -> uint64_t { return p.nlong; },   // units
+        [](const spmv_plan &) -> uint64_t { return kGoldLong; },  // unit_nnz
+        one_block,
+        [](const spmv_plan &) -> int { return 0; },            // format_bits
+        [](const spmv_plan &p) -> uint64_t { return p.nnz; },  // stored_entries
+        [](const spmv_plan &p) -> void * { return p.d_col; },  // index_stream
+        -1, {0, 0}, set_tile_variant, false,  // tune_slot, product_variants, set_variant, host_y
+    };
+}
+const layout_ops &gold_layout()
+{
+    static const layout_ops row = csr_row("gold", build_gold);
+    return row;
+}
+const layout_ops &fpga_layout()
+{
+    static const layout_ops row = csr_row("fpga", build_fpga);
+    return row;
+}
+
 }  // namespace spmvhw

@@ -1,5 +1,5 @@
-// Host-only layout planner of the panel-sweep and binned builds (spmv_host.hpp): panels, the
-// sweep's work units, binned's windows, segments and pass-1 units. No HIP and no environment; like
+// Host-only layout planner of the panel-sweep, binned and tile builds (spmv_host.hpp): panels, the
+// sweep's work units, binned's windows, segments and pass-1 units, the tiles' tables. No HIP and no environment; like
 // host.cpp it is also built by tests/sanitize/Makefile (host_check layout).
 #include <algorithm>
 #include <cmath>
@@ -212,6 +212,67 @@ void plan_bin_units(const std::vector<uint32_t> &cnt, const std::vector<uint32_t
             out.uwin.push_back((uint32_t)w);
         }
     }
+}
+
+int plan_tiles(const IndexType *h_rp, IndexType n, uint64_t nnz, bool has_empty, tile_plan &out)
+{
+    out.nnz_pad = (nnz + kTileNnz - 1) / kTileNnz * kTileNnz;
+    const uint64_t ntiles = out.ntiles = out.nnz_pad / kTileNnz;
+    std::vector<uint32_t> &rowend = out.rowend, &tile_info = out.tile_info, &cross = out.cross;
+    rowend.assign(out.nnz_pad / 32, 0u);
+    out.row_id.clear();
+    for (IndexType r = 0; r < n; ++r) {
+        if (h_rp[r + 1] > h_rp[r]) {
+            const uint64_t e = h_rp[r + 1] - 1ull;
+            rowend[e >> 5] |= 1u << (e & 31);
+            if (has_empty)
+                out.row_id.push_back(r);
+        }
+    }
+    auto bit = [&](uint64_t k) { return (rowend[k >> 5] >> (k & 31)) & 1u; };
+    tile_info.assign(ntiles + 1, 0u);
+    uint64_t rr = 0, c = 0;
+    for (uint64_t t = 0; t <= ntiles; ++t) {
+        const uint64_t k = t * kTileNnz;
+        while (rr < n && h_rp[rr + 1] <= k) {
+            if (h_rp[rr + 1] > h_rp[rr])
+                ++c;
+            ++rr;
+        }
+        if (c > 0x7FFFFFFFull) {
+            set_error("too many non-empty rows for the tile table");
+            return 1;
+        }
+        const bool cont = k > 0 && k < nnz && !bit(k - 1);
+        tile_info[t] = (uint32_t)(c << 1) | (cont ? 1u : 0u);
+    }
+    // rows crossing tile boundaries (structural): tile t "has a tail" when its last entry is not
+    // a row end and entries follow; a crossing starts at a tile with a tail whose row began in
+    // it, and ends at the next tile that contains a row end
+    cross.clear();
+    std::vector<uint8_t> has_tail(ntiles, 0), has_end(ntiles, 0);
+    for (uint64_t t = 0; t < ntiles; ++t) {
+        const uint64_t w0 = t * (kTileNnz / 32);
+        for (uint64_t w = 0; w < kTileNnz / 32; ++w)
+            has_end[t] |= rowend[w0 + w] != 0;
+        const uint64_t last = (t + 1) * kTileNnz - 1;
+        has_tail[t] = (last + 1 < nnz) && !bit(last);
+    }
+    for (uint64_t t = 0; t < ntiles; ++t) {
+        if (!has_tail[t] || !(has_end[t] || t == 0 || !has_tail[t - 1]))
+            continue;
+        uint64_t j = t + 1;
+        while (j < ntiles && !has_end[j])
+            ++j;
+        if (j >= ntiles) {
+            set_error("internal: unterminated row crossing");
+            return 1;
+        }
+        cross.push_back(tile_info[t + 1] >> 1);
+        cross.push_back((uint32_t)t);
+        cross.push_back((uint32_t)j);
+    }
+    return 0;
 }
 
 }  // namespace spmvhw

@@ -121,14 +121,13 @@ static int multi_create(spmv_multi **out, int device, int op, const csr_slice &s
     }
     const IndexType nr_rows = sl.n, nr_cols = sl.m;
     hipStream_t s = (hipStream_t)sl.stream;
-    const char *env = std::getenv("SPMV_HW_KERNEL");
-    const bool automatic = !env || !*env || !std::strcmp(env, "auto");
+    const int requested = requested_kernel();  // env SPMV_HW_KERNEL
     bool native = false;
     int sweep_nvec = 1;  // > 1: plan_create_from_slice may build the multi-vector sweep
     if (multi_native_nvec(nvec)) {
-        if (env && !std::strcmp(env, "slices")) {
+        if (requested == kKernelSlices) {
             native = true;
-        } else if (automatic && nr_rows) {
+        } else if (requested == -1 && nr_rows) {
             const uint64_t nnz = sl.nnz(), stored = slice_stored_entries(sl.rp.data(), nr_rows);
             native = nnz > 0 && stored <= 0xFFFFFFFFull && double(stored) <= multi_pad_limit(nvec) * double(nnz);
             // the slice rule declines: a candidate for the sweep (plan_create_from_slice decides

@@ -696,4 +696,34 @@ int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
     return 0;
 }
 
+// ---- the slices' row of the layout table (spmv_internal.hpp layout_ops) ----
+static uint64_t slices_device_bytes(const spmv_plan &p)  // padded entries, slot bases, slice offsets, row lengths
+{
+    return p.slice_slots * kWave * (sizeof(ValueType) + p.slice_off_bytes) + p.slice_slots * (p.slice_clustered ? 16 : 4) +
+           (p.nslices + 1) * 4 +
+           uint64_t(p.nr_rows) * 4;
+}
+
+static int slices_format_bits(const spmv_plan &p)
+{
+    return (p.slice_off_bytes < 4 ? 1 : 0) | (p.slice_off_bytes == 1 ? 8 : 0) | (p.slice_clustered ? 16 : 0);
+}
+
+const layout_ops &slices_layout()
+{
+    static const layout_ops row = {
+        "slices", "build slice layout", build_slices, kKernelTiles,  // (> 2^32 stored entries, or the padding limit)
+        nullptr, launch_of<launch_slices>, nullptr, warm_of<launch_slices>,
+        slices_device_bytes,
+        [](const spmv_plan &p) -> uint64_t { return p.nslices; },              // units
+        [](const spmv_plan &p) -> uint64_t { return p.slice_slots * kWave; },  // unit_nnz: stored entries with padding
+        one_block,
+        slices_format_bits,
+        [](const spmv_plan &p) -> uint64_t { return p.slice_slots * kWave; },  // stored_entries
+        [](const spmv_plan &p) -> void * { return p.d_colnar; },               // index_stream
+        2, {0, 0}, set_tile_variant, false,  // tune_slot, product_variants, set_variant, host_y
+    };
+    return row;
+}
+
 }  // namespace spmvhw

@@ -56,8 +56,8 @@ int slice_device_args(const char *who, const void *handle, IndexType n, const In
 // message names <who>), offsets col / val and checks that rp does not decrease.
 int slice_rebase(const char *who, csr_slice &s, const IndexType *nr_nzeros = nullptr);
 
-// Layout planner of the panel-sweep and binned builds (layout.cpp): the host arithmetic that decides
-// a plan's panels, work units, windows and segments. Pure functions of their arguments: no HIP and
+// Layout planner of the panel-sweep, binned and tile builds (layout.cpp): the host arithmetic that decides
+// a plan's panels, work units, windows, segments and tile tables. Pure functions of their arguments: no HIP and
 // no environment -- build_sweep / build_binned read the switches and pass them in.
 constexpr uint64_t kSweepLdsBytes = 160 * 1024;       // LDS of one CU holds the panel's y
 constexpr uint64_t kSweepChunk = 128;                 // entries per packed chunk (one wave, 2 per lane)
@@ -129,6 +129,24 @@ struct bin_units {
 };
 void plan_bin_units(const std::vector<uint32_t> &cnt, const std::vector<uint32_t> &esc, uint64_t nwin, uint64_t P,
                     uint64_t cus, bin_units &out);
+
+// The tile build's host arithmetic (layout.cpp; build_tiles uploads the result): the flagged-tile
+// representation of spmv_internal.hpp's head comment over tiles of kTileNnz entries.
+constexpr int kWave = 64;
+constexpr int kLaneEntries = 4;               // entries per lane per wave step
+constexpr int kStep = kWave * kLaneEntries;   // 256 entries per wave step
+constexpr int kTileSteps = 2;                 // wave steps per tile
+constexpr int kTileNnz = kStep * kTileSteps;  // 512 entries per wave tile
+struct tile_plan {
+    uint64_t nnz_pad = 0, ntiles = 0;  // nnz rounded up to whole tiles
+    std::vector<uint32_t> rowend;      // bit k set <=> entry k ends its row [nnz_pad / 32]
+    std::vector<uint32_t> tile_info;   // (non-empty rows ended before the tile << 1) | continues a row [ntiles + 1]
+    std::vector<uint32_t> row_id;      // the non-empty rows in order; filled only when has_empty
+    std::vector<uint32_t> cross;       // (row, first tile, last tile) of every row in more than one tile
+};
+// Returns 0, or 1 with the error "too many non-empty rows for the tile table" or "internal:
+// unterminated row crossing".
+int plan_tiles(const IndexType *h_rp, IndexType n, uint64_t nnz, bool has_empty, tile_plan &out);
 
 // wall clock in microseconds (util.cpp:3-8)
 double timestamp_us();

@@ -32,11 +32,7 @@
 
 namespace spmvhw {
 
-constexpr int kWave = 64;
-constexpr int kLaneEntries = 4;                    // entries per lane per wave step
-constexpr int kStep = kWave * kLaneEntries;        // 256 entries per wave step
-constexpr int kTileSteps = 2;                      // wave steps per tile
-constexpr int kTileNnz = kStep * kTileSteps;       // 512 entries per wave tile
+// (kWave, kStep, kTileSteps, kTileNnz: spmv_host.hpp, with the tile planner)
 constexpr int kBlockThreads = 256;                 // 4 waves = 4 tiles per workgroup
 constexpr int kSweepThreads = 1024;                // default panel-sweep workgroup (16 waves, 1/CU)
 constexpr int kSweepTurn = 91;         // sweep variant: ordered LDS adds (deterministic y), the
@@ -72,13 +68,24 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v0)
 
 }  // namespace spmvhw
 
-struct spmv_plan {
+// What a plan knows before any layout is built: plan_create_from_slice fills it once, and every
+// candidate layout (the tuner's, the automatic slice attempt, the multi-vector sweep) starts
+// from a copy.
+struct plan_seed {
     int device = 0;
     IndexType nr_rows = 0, nr_cols = 0;
-    uint64_t nnz = 0, nnz_pad = 0;
+    uint64_t nnz = 0;
     uint64_t nzr = 0;          // non-empty rows
-    uint64_t ntiles = 0;
     bool has_empty = false;
+    int sweep_threads = spmvhw::kSweepThreads;  // workgroup size: 1024, 512 or 256 (env SPMV_SWEEP_THREADS)
+    double locality = -1.0;    // probe result used by the automatic kernel choice
+};
+
+struct spmv_plan : plan_seed {
+    spmv_plan() = default;
+    explicit spmv_plan(const plan_seed &seed) : plan_seed(seed) {}
+    uint64_t nnz_pad = 0;
+    uint64_t ntiles = 0;
     int kernel = 0;
     int op = SPMV_OP_N;        // SPMV_OP_T: the plan holds A^T of the slice it was created from
     int variant = 0;           // tile-kernel variant bits (spmv_plan_set_variant)
@@ -149,8 +156,7 @@ struct spmv_plan {
                                        // write_panel); null (default): k_sweep_combine
     int sweep_acc_bytes = 8;           // LDS accumulator: 8 (fp64) or 4 (fp32 via CAS, env SPMV_SWEEP_ACC=32)
     uint32_t panel_rmax = 0;
-    int sweep_threads = spmvhw::kSweepThreads;  // workgroup size: 1024, 512 or 256 (env SPMV_SWEEP_THREADS)
-    int sweep_nvec = 1;              // > 1: spmv_multi's one-pass sweep plan, panels sized for this many
+    int sweep_nvec = 1;             // > 1: spmv_multi's one-pass sweep plan, panels sized for this many
                                      // accumulators per row, unpacked entries, never split; run only by
                                      // launch_sweep_multi (sweep_multi.hip)
     uint32_t *d_s_col = nullptr;
@@ -205,7 +211,6 @@ struct spmv_plan {
     uint32_t y_epoch = 0;
     ValueType *y_host = nullptr;  // (tools build, SPMV_HW_DIRECT=1) the sweep stores y here instead
                                   // of d_y: mapped pinned host memory
-    double locality = -1.0;    // probe result used by the automatic kernel choice
     double tuned_ms[4] = {-1.0, -1.0, -1.0, -1.0};  // SPMV_HW_KERNEL=tune: tiles / sweep / slices / binned ms
 
     // timing (HIP events around the main kernel, on the launch stream)
@@ -241,6 +246,57 @@ inline void launch_or_warm(bool warm, K kernel, dim3 grid, dim3 block, size_t ld
     }
 }
 
+// What a kernel id means to the host (DESIGN.md §3 "The layout table"): one row per kKernel*
+// id, defined beside its kernel. A new layout is one new row plus its file. (A row is a constant
+// inside its accessor: at namespace scope the device compilation would emit it too, and it
+// names host functions.)
+struct layout_ops {
+    const char *name;         // the SPMV_HW_KERNEL spelling
+    const char *trace_label;  // the build's label under SPMV_HW_TRACE
+    // 0 ok, 1 error, 2 the layout cannot hold this matrix: an automatic plan takes decline_to
+    int (*build)(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col, const ValueType *d_val, hipStream_t s);
+    int decline_to;  // -1: none
+    // one SpMV: before (may be null), launch -- the main kernel, what the timing events bracket --
+    // and after (may be null); only kernels and memsets, so the sequence is capturable
+    hipError_t (*before)(const spmv_plan &p, ValueType *d_y, hipStream_t s);
+    hipError_t (*launch)(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s);
+    hipError_t (*after)(const spmv_plan &p, ValueType *d_y, hipStream_t s);
+    void (*warm)(const spmv_plan &p, hipStream_t s);  // loads the code objects of the above, no launch
+    uint64_t (*device_bytes)(const spmv_plan &p);
+    uint64_t (*units)(const spmv_plan &p);     // spmv_plan_stats.nr_tiles: work units of the main kernel
+    uint64_t (*unit_nnz)(const spmv_plan &p);  // spmv_plan_stats.tile_nnz
+    uint32_t (*blocks)(const spmv_plan &p);    // spmv_plan_stats.blocks
+    int (*format_bits)(const spmv_plan &p);    // the layout's bits of spmv_plan_stats.format
+    uint64_t (*stored_entries)(const spmv_plan &p);  // spmv_hw's hw_matrix: entries with padding,
+    void *(*index_stream)(const spmv_plan &p);       // and the device array that holds their indices
+    int tune_slot;                             // index into spmv_plan::tuned_ms; -1: not a tune candidate
+    int product_variants[2];                   // what the product library accepts beside 0 (0: nothing more)
+    int (*set_variant)(spmv_plan &p, int variant);  // 0, or 1 with the error set
+    bool host_y;                               // the kernel can store y to spmv_plan::y_host (tools build)
+};
+const layout_ops &tiles_layout(), &gold_layout(), &sweep_layout(), &fpga_layout(), &blocked_layout(), &slices_layout(),
+    &binned_layout();
+const layout_ops &layout_of(int kernel);  // plan.cpp: the rows by kernel id
+constexpr int kKernelCount = 7;
+// a launcher with a warm flag as a row's launch and warm entries
+using launcher = hipError_t(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm);
+template <launcher F>
+hipError_t launch_of(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s)
+{
+    return F(p, d_x, d_y, s, false);
+}
+template <launcher F>
+void warm_of(const spmv_plan &p, hipStream_t s)
+{
+    (void)F(p, nullptr, nullptr, s, true);
+}
+inline uint32_t one_block(const spmv_plan &) { return 1; }
+inline int set_tile_variant(spmv_plan &p, int variant)  // the tile kernel's two variant bits (every CSR-order row too)
+{
+    p.variant = variant & 3;
+    return 0;
+}
+
 // kernels.hip
 hipError_t launch_spmv(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm = false);
 hipError_t launch_fixup(const spmv_plan &p, ValueType *d_y, hipStream_t s, bool warm = false);
@@ -263,6 +319,7 @@ hipError_t launch_narrow(const uint32_t *d_col, uint64_t nnz, uint64_t nnz_pad, 
 
 // gold.hip
 hipError_t launch_gold(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm = false);
+int fpga_params(spmv_plan &p);  // fpga_vf / fpga_width from env SPMV_FPGA_VF / SPMV_FPGA_BLOCK (kernels 3 and 4)
 
 // blocked.hip
 hipError_t launch_blocked(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm = false);
@@ -298,7 +355,6 @@ struct sweep_behind {
 hipError_t launch_sweep(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm = false,
                         int phase = 0, void *part = nullptr, const sweep_behind *behind = nullptr);
 bool sweep_behind_ok(const spmv_plan &p);  // the plan's sweep launch can carry a combine behind
-bool product_variant(int kernel, int variant);  // spmv_plan_set_variant: accepted by the product library
 // 0 ok, 1 error, 2 the padded layout would overflow 32-bit entry offsets (caller may use tiles)
 int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, const ValueType *d_val_src,
                 hipStream_t s);
@@ -361,7 +417,23 @@ inline int device_cu_count(int device)
                : 256;
 }
 
-// plan.cpp helpers shared with the wrapper
+// plan.cpp
+constexpr int kKernelTune = -2;
+// env SPMV_HW_KERNEL (its only reader): a kernel id by its row's name, kKernelTune for "tune",
+// -1 for the automatic choice (unset, "auto", or no row's name)
+int requested_kernel();
+// Enqueues one SpMV on s by the plan's row: before, launch (between a timing event pair when
+// `timing`), after
+int run_impl(spmv_plan *p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool timing);
+// the plan's next timing event pair (created on first use), e0 recorded on s
+int timing_begin(spmv_plan *p, hipStream_t s, hipEvent_t *e1);
+
+// graph.cpp
+// ms per SpMV of a built layout on scratch x / y (SPMV_HW_KERNEL=tune)
+int time_layout(spmv_plan &P, const ValueType *d_x, ValueType *d_y, hipStream_t s, double *ms);
+int graph_form(const spmv_plan *p);  // how spmv_plan_run_graph captures: 0 serial chain, 1 two-stream DAG, 2 behind
+
+// upload.cpp
 int upload_staged(void *dst, const void *src, size_t bytes, hipStream_t s);  // pageable H2D, synchronous
 // Fills `out` (spmv_host.hpp) from device arrays: slice_device_args, then hipSetDevice, row_ptr
 // copied to the host on `stream`, slice_rebase against nr_nzeros.
@@ -372,7 +444,7 @@ int slice_from_device(const char *who, csr_slice &out, const void *handle, int d
 // up_col / up_val on the slice's stream
 int slice_entries_on_device(const csr_slice &sl, device_scratch &up_col, device_scratch &up_val,
                             const IndexType **d_col, const ValueType **d_val);
-// The plan of the slice (op = SPMV_OP_T: of its device transpose, transpose_slice, the plan's op set).
+// plan.cpp: the plan of the slice (op = SPMV_OP_T: of its device transpose, transpose_slice, the plan's op set).
 // force_kernel >= 0: that kernel as if env SPMV_HW_KERNEL named it (spmv_multi's slice path).
 // multi_nvec > 1 (spmv_multi's one-pass sweep), with force_kernel = -1: the sweep plan is built
 // with that many accumulators per row (spmv_plan::sweep_nvec) when the automatic choice for the

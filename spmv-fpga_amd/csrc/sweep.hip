@@ -1353,6 +1353,7 @@ bool sweep_can_flag_panels(const spmv_plan &p)
 
 bool sweep_behind_ok(const spmv_plan &p)
 {
+    // (packed, delta-coded entries: only build_sweep makes them, so any other layout's plan says no)
     if (!p.sweep_packed || !p.sweep_delta || p.sweep_det || p.sweep_split < 2 || p.d_panel_cnt)
         return false;
     switch (p.sweep_variant) {
@@ -1705,6 +1706,68 @@ int probe_locality(const IndexType *d_rp, const IndexType *d_col, IndexType n, h
     SPMV_TRY(hipFree(d_cnt));
     *frac = h[0] ? double(h[1]) / double(h[0]) : 1.0;
     return 0;
+}
+
+// ---- the sweep's row of the layout table (spmv_internal.hpp layout_ops) ----
+static hipError_t sweep_launch(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s)
+{
+    return launch_sweep(p, d_x, d_y, s);
+}
+
+static void sweep_warm(const spmv_plan &p, hipStream_t s)
+{
+    if (p.sweep_nvec > 1)  // spmv_multi's plan: run only by launch_sweep_multi
+        (void)launch_sweep_multi(p, p.sweep_nvec, nullptr, nullptr, s, true);
+    else
+        (void)launch_sweep(p, nullptr, nullptr, s, true);
+}
+
+static uint64_t sweep_device_bytes(const spmv_plan &p)
+{
+    return p.ent_pad * ((p.d_s_col ? sizeof(uint32_t) : 0) + (p.sweep_packed ? 0 : sizeof(uint16_t)) + sizeof(ValueType)) +
+           (p.npanels + 1) * 4 + (p.nunits + 1) * 4 + (p.sweep_packed ? p.ent_pad / kSweepChunk * 4 : 0) +
+           (p.sweep_split > 1 ? p.nunits * (uint64_t(p.panel_rmax) + 1) * p.sweep_acc_bytes : 0) + p.nunits * 4 + (p.npanels + 1) * 4 +
+           (p.d_panel_cnt ? p.npanels * 4 : 0) +
+           (p.sweep_delta ? p.ent_pad * 3 + p.ent_pad / kSweepChunk * 4 + p.sweep_side_chunks * kSweepChunk * 4 : 0);
+}
+
+static int sweep_format_bits(const spmv_plan &p)
+{
+    const bool stealing = p.sweep_steal && p.sweep_variant >= 37 && p.sweep_variant <= 39;
+    return (p.sweep_packed ? 2 : 0) | (p.sweep_lane_order ? 4 : 0) | (p.sweep_delta ? 64 : 0) | (stealing ? 128 : 0) |
+           (p.sweep_split > 1 && p.xbias_split > 0.0 ? 1024 : 0) | (p.sweep_split > 1 && p.xbias_split < 0.0 ? 2048 : 0) |
+           (p.sweep_wide ? 4096 : 0) | (p.sweep_nvec > 1 ? 8192 : 0);
+}
+
+static int sweep_set_variant(spmv_plan &p, int variant)
+{
+    // 0 = the plan's default form in both builds: 28 (the tools library's unpacked measurement
+    // form that used to sit at 0 is variant 40)
+    if (variant == 0)
+        variant = 28;
+    // every variant but the default (28), 36 (the same) and the measurement build's stealing
+    // variants 37-39 reads the 12-byte rc words, which a delta plan rebuilds on first use
+    if ((variant < 36 || variant > 39) && variant != 28 && sweep_materialize_rc(p))
+        return 1;
+    p.sweep_variant = variant;
+    return 0;
+}
+
+const layout_ops &sweep_layout()
+{
+    static const layout_ops row = {
+        "sweep", "build sweep layout", build_sweep, kKernelTiles,  // (32-bit entry offsets overflow: the tiles have none)
+        nullptr, sweep_launch, nullptr, sweep_warm,
+        sweep_device_bytes,
+        [](const spmv_plan &p) -> uint64_t { return p.nunits; },                             // units: panel pieces
+        [](const spmv_plan &p) -> uint64_t { return p.nunits ? p.ent_pad / p.nunits : 0; },  // unit_nnz
+        one_block,
+        sweep_format_bits,
+        [](const spmv_plan &p) -> uint64_t { return p.ent_pad; },                                           // stored_entries
+        [](const spmv_plan &p) -> void * { return p.d_s_col ? (void *)p.d_s_col : (void *)p.d_s_row16; },  // index_stream
+        1, {28, kSweepTurnOrdered}, sweep_set_variant, true,  // tune_slot, product_variants, set_variant, host_y
+    };
+    return row;
 }
 
 }  // namespace spmvhw

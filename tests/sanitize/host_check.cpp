@@ -10,6 +10,8 @@
 //   host_check slice                       slice_from_host on whole, empty, last-row and random ranges
 //   host_check layout                      the sweep / binned layout planner (layout.cpp): invariants of
 //                                          panels, units, windows and segments; pinned edge cases
+//   host_check tiles                       the tile planner (layout.cpp plan_tiles): bitmap, tile table, row map
+//                                          and crossings against a per-entry recomputation; pinned edge cases
 //   host_check schedule                    every exchange at 1..8 ranks, rows covered once
 //   host_check accumulate                  producer threads land parts while 16 threads add them
 //   host_check verify                      verification / storage_overhead semantics
@@ -455,6 +457,89 @@ static int cmd_layout()
     return 0;
 }
 
+// ---- the tile planner (layout.cpp plan_tiles) against a per-entry recomputation ----
+
+static void check_tiles(const std::vector<uint32_t> &len)
+{
+    const std::vector<IndexType> rp = row_ptr_of(len);
+    const IndexType n = IndexType(len.size());
+    const uint64_t nnz = rp[n];
+    // entry by entry: the compact index (among the non-empty rows) of the row that holds it
+    std::vector<uint32_t> owner(nnz), ids;
+    for (IndexType r = 0; r < n; ++r) {
+        for (uint64_t k = rp[r]; k < rp[r + 1]; ++k)
+            owner[k] = uint32_t(ids.size());
+        if (len[r])
+            ids.push_back(r);
+    }
+    for (int has_empty = 0; has_empty < 2; ++has_empty) {
+        if (!has_empty && ids.size() < n)
+            continue;  // (the build passes has_empty = some row is empty; with none, both forms)
+        tile_plan t;
+        set_error("");
+        CHECK(plan_tiles(rp.data(), n, nnz, has_empty != 0, t) == 0 && !std::strlen(get_error()));
+        CHECK(t.nnz_pad == (nnz + 511) / 512 * 512 && t.ntiles == t.nnz_pad / 512);
+        CHECK(t.rowend.size() == t.nnz_pad / 32 && t.tile_info.size() == t.ntiles + 1);
+        // bitmap bits: exactly the row ends (none in the padding)
+        for (uint64_t k = 0; k < t.nnz_pad; ++k) {
+            const bool end = k < nnz && (k + 1 == nnz || owner[k + 1] != owner[k]);
+            CHECK(((t.rowend[k >> 5] >> (k & 31)) & 1u) == (end ? 1u : 0u));
+        }
+        // tile_info[t]: non-empty rows ended before entry 512 t, and whether that entry continues a row
+        for (uint64_t i = 0; i <= t.ntiles; ++i) {
+            const uint64_t k = 512 * i;
+            const uint32_t ended = k == 0 ? 0 : k >= nnz ? uint32_t(ids.size()) : owner[k - 1] + (owner[k] != owner[k - 1]);
+            const bool cont = k > 0 && k < nnz && owner[k] == owner[k - 1];
+            CHECK(t.tile_info[i] == ((ended << 1) | (cont ? 1u : 0u)));
+        }
+        // row_id: the non-empty rows in order (only kept when some row is empty)
+        CHECK(t.row_id == (has_empty ? ids : std::vector<uint32_t>()));
+        // crossings: every non-empty row whose first and last entries lie in different tiles, in row order
+        std::vector<uint32_t> want;
+        for (uint32_t c = 0; c < ids.size(); ++c) {
+            const uint64_t first = rp[ids[c]] / 512, last = (uint64_t(rp[ids[c] + 1]) - 1) / 512;
+            if (last > first) {
+                want.push_back(c);
+                want.push_back(uint32_t(first));
+                want.push_back(uint32_t(last));
+            }
+        }
+        CHECK(t.cross == want);
+    }
+}
+
+static int cmd_tiles()
+{
+    check_tiles({});           // no rows
+    check_tiles({0, 0, 0});    // nnz = 0
+    check_tiles({1});          // nnz = 1
+    check_tiles({0, 1, 0});
+    check_tiles({512});        // exactly one tile, in one row
+    check_tiles({513});
+    check_tiles({200, 312});   // nnz = 512 ending on a tile edge
+    check_tiles({200, 312, 1});  // nnz = 513
+    check_tiles({100, 1500, 7});  // one row over two tile boundaries, its crossing ending in a later tile
+    check_tiles({1500});
+    check_tiles({500, 12, 3});     // a row ending exactly on entry 511
+    check_tiles({512, 512, 512});  // every row a whole tile: no crossing
+    check_tiles({0, 0, 5, 0, 0, 600, 0, 3, 0, 0});  // leading, interior and trailing empty rows
+    {
+        std::vector<uint32_t> last(300, 0);  // all rows empty but the last
+        last.back() = 1100;
+        check_tiles(last);
+    }
+    std::mt19937_64 g(23);
+    for (int it = 0; it < 300; ++it) {
+        std::vector<uint32_t> len(g() % 400);
+        const bool holes = it % 3 != 0;
+        for (auto &l : len)
+            l = g() % 50 == 0 ? 600 + uint32_t(g() % 601) : uint32_t(g() % 41) + (holes ? 0 : 1);
+        check_tiles(len);
+    }
+    std::printf("OK tiles\n");
+    return 0;
+}
+
 static int cmd_schedule()
 {
     std::mt19937_64 g(9);
@@ -616,12 +701,14 @@ int main(int argc, char **argv)
         return cmd_slice();
     if (argc >= 2 && !std::strcmp(argv[1], "layout"))
         return cmd_layout();
+    if (argc >= 2 && !std::strcmp(argv[1], "tiles"))
+        return cmd_tiles();
     if (argc >= 2 && !std::strcmp(argv[1], "schedule"))
         return cmd_schedule();
     if (argc >= 2 && !std::strcmp(argv[1], "accumulate"))
         return cmd_accumulate();
     if (argc >= 2 && !std::strcmp(argv[1], "verify"))
         return cmd_verify();
-    std::fprintf(stderr, "usage: host_check read <mtx> <out> | partition | slice | layout | schedule | accumulate | verify\n");
+    std::fprintf(stderr, "usage: host_check read <mtx> <out> | partition | slice | layout | tiles | schedule | accumulate | verify\n");
     return 2;
 }

@@ -283,7 +283,7 @@ def test_deterministic_kernel_ships_only_its_ordered_forms(dtype):
     assert ords == {"0"}, ords  # ORD 1 (variant 91) is a measurement variant: tools library
 
 
-# what spmv_plan_set_variant accepts in the product library, per kernel (plan.cpp product_variant)
+# what spmv_plan_set_variant accepts in the product library, per kernel (the layout rows' product_variants)
 PRODUCT_VARIANTS = {"tiles": {0}, "gold": {0}, "sweep": {0, 28, 94}, "fpga": {0}, "blocked": {0},
                     "slices": {0}, "binned": {0, 1, 2}}
 KERNEL_IDS = {"tiles": 0, "gold": 1, "sweep": 2, "fpga": 3, "blocked": 4, "slices": 5, "binned": 6}
@@ -325,16 +325,33 @@ def test_product_refuses_every_measurement_variant(monkeypatch, kernel):
 
 
 def test_product_variant_table_matches_the_source():
-    """The CPU side of the same check: plan.cpp's product_variant lists exactly the variants above
-    (the measurement variants' kernel forms are compiled only under -DSPMV_ABLATIONS)."""
-    src = open(os.path.join(ROOT, "spmv-fpga_amd", "csrc", "plan.cpp")).read()
-    body = src[src.index("bool product_variant(int kernel, int variant)"):]
+    """The CPU side of the same check: the layout table's rows (layout_ops::product_variants, one
+    row beside each kernel) list exactly the variants above beside 0, and spmv_plan_set_variant
+    refuses everything else in the product build (the measurement variants' kernel forms are
+    compiled only under -DSPMV_ABLATIONS)."""
+    csrc = os.path.join(ROOT, "spmv-fpga_amd", "csrc")
+    names = {"28": 28, "kSweepTurnOrdered": 94, "0": 0, "1": 1, "2": 2}
+    rows = {}
+    for f in os.listdir(csrc):
+        text = open(os.path.join(csrc, f)).read()
+        for row in re.findall(r"static const layout_ops row = (?:\{\n\s*\"(\w+)\"|csr_row\(\"(\w+)\")", text):
+            rows[row[0] or row[1]] = text
+    assert sorted(rows) == sorted(PRODUCT_VARIANTS)
+    for kernel, text in rows.items():
+        listed = re.findall(r"\{(\w+),\s*(\w+)\},\s*\w*set_\w*variant\b", text)  # product_variants, then set_variant
+        assert len(listed) == 1, kernel  # one row per file (gold and fpga share csr_row's)
+        assert {0} | {names[v] for v in listed[0]} == PRODUCT_VARIANTS[kernel], kernel
+    plan = open(os.path.join(csrc, "plan.cpp")).read()
+    body = plan[plan.index("int spmv_plan_set_variant(spmv_plan *p, int variant)"):]
     body = body[:body.index("\n}\n")]
-    assert "variant == 0" in body
-    assert "kKernelSweep)\n        return variant == 28 || variant == kSweepTurnOrdered;" in body
-    assert "kKernelBinned)\n        return variant == 1 || variant == 2;" in body
-    assert body.rstrip().endswith("return false;")
-    sweep = open(os.path.join(ROOT, "spmv-fpga_amd", "csrc", "sweep.hip")).read()
+    gate = ("#ifndef SPMV_ABLATIONS", "variant != 0", "variant != L.product_variants[0]",
+            "variant != L.product_variants[1]", "tools library only", "return 1;", "#endif", "L.set_variant(*p, variant)")
+    at = 0
+    for g in gate:  # in this order
+        assert g in body[at:], g
+        at = body.index(g, at) + len(g)
+    assert "const layout_ops &L = layout_of(p->kernel);" in body
+    sweep = open(os.path.join(csrc, "sweep.hip")).read()
     head = sweep[:sweep.index("case 15: PK(2, 0); break;")]
     assert head.rfind("#ifdef SPMV_ABLATIONS") > head.rfind("#endif")
 

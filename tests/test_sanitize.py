@@ -57,7 +57,7 @@ def _run(binary, *args, threads=None, timeout=300):
 
 
 @pytest.mark.parametrize("kind", list(BINS))
-@pytest.mark.parametrize("cmd", ["partition", "slice", "layout", "schedule", "accumulate", "verify"])
+@pytest.mark.parametrize("cmd", ["partition", "slice", "layout", "tiles", "schedule", "accumulate", "verify"])
 def test_host_checks_clean_under_sanitizer(built, kind, cmd):
     p = _run(built[kind], cmd)
     assert p.returncode == 0, p.stdout + p.stderr

@@ -10,7 +10,7 @@ automatically chosen kernel, which is what sets the automatic choice's padding l
 where the automatic choice takes it against the fallback on the automatically chosen kernel;
 with --alt-lib-dir a second build's one-pass sweep beside them.
 
-Protocol (that of plan.cpp time_layout): each form is captured into a graph of --steps runs on
+Protocol (that of graph.cpp time_layout): each form is captured into a graph of --steps runs on
 one stream; one untimed replay, then --reps replays each bracketed by events; the two forms of a
 pair alternate, round by round. A line reports the median, min and max ms per step over all
 rounds, the modelled bytes of the form and the resulting TB/s. One JSON line per form is appended

@@ -9,7 +9,7 @@ non-zeros) and precision:
     device idle before and after; the N create is the code path without an op);
   - one SpMV of the T plan against one of the N plan, by graph replay: --steps runs captured into
     one graph, one untimed replay, then --reps replays each between an event pair, the two plans
-    alternating round by round (the form of plan.cpp time_layout); median, min and max ms per run;
+    alternating round by round (the form of graph.cpp time_layout); median, min and max ms per run;
   - the kernel the automatic choice took for A and for A^T, and with --forced, the T plan built
     with each of those kernels forced (SPMV_HW_KERNEL) and timed the same way, which shows whether
     the automatic choice took the fastest kernel for A^T.
