@@ -349,6 +349,57 @@ typedef struct spmv_xop {
 #define SPMV_XBUF_XNEXT 3  /* all-gather: the full-length next x of every rank */
 int spmv_mgpu_schedule(int exchange, int rank, int nranks, const IndexType *bounds, spmv_xop *ops, int cap);
 
+/* ---------------- Part 5: sparse triangular solve ----------------
+ * A spmv_trsv solves T x = b, T being the `uplo` triangle of a square n x n CSR matrix A: entries on
+ * the other side of the diagonal are ignored, so a full symmetric A gives the two Gauss-Seidel sweeps
+ * (one LOWER and one UPPER handle) without the caller splitting anything. d_row_ptr may start at any
+ * offset (as for spmv_plan_create_device); the columns inside a row need not be sorted; duplicate
+ * (r, c) entries each take part, in CSR order, and duplicate diagonal entries are added in CSR order.
+ *   diag = SPMV_TRSV_DIAG_UNIT: stored diagonal entries are ignored and the diagonal is 1.
+ *   diag = SPMV_TRSV_DIAG_NONUNIT: a row without a stored diagonal entry is refused at create
+ *     ("... missing diagonal in row r", the first such row); a stored diagonal that is numerically
+ *     zero is the caller's business (IEEE division).
+ *   A column index >= n is refused ("column index out of range").
+ * Create is host work: the rows' dependency levels (level 0: no off-diagonal entry in the triangle;
+ * else 1 + the highest level among the row's columns), the rows sorted by level, and the
+ * off-diagonal triangle repacked in that order and uploaded. A device slice's col_ind and values
+ * are copied back to the host once for it; the call returns when the handle is complete.
+ * spmv_trsv_solve: x_i = (b_i - sum_{j != i} t_ij x_j) / d_i, one true division per row, no stored
+ * reciprocal (a diagonal-only T gives b / d bit for bit). It overwrites d_x, is asynchronous on
+ * `stream` and enqueues only kernels, one after the other (capturable into the caller's hipGraph as
+ * a linear chain): one launch per dependency level, runs of narrow levels (at most 1024 rows each)
+ * sharing one single-workgroup launch. Nothing is allocated or synchronised, and no workgroup waits
+ * for another inside a launch. The order of a row's additions is fixed by the layout, and there are
+ * no atomics: two runs, and two handles of the same input, give the same bits. d_x == d_b (exactly)
+ * is allowed; any other overlap is undefined. A run writes nothing the handle owns, so runs of one
+ * handle may overlap one another. Reads no environment switch.
+ * A bad uplo or diag, a null handle or out-pointer, a null row_ptr with n > 0 or a null d_b / d_x
+ * with n > 0 returns nonzero before any HIP call. n == 0 gives an empty handle whose solve enqueues
+ * nothing. Not for spmv_mgpu_* nor Part 1; for a transposed solve build the handle from
+ * spmv_csr_transpose_device's output. */
+typedef struct spmv_trsv spmv_trsv;
+#define SPMV_TRSV_LOWER 0
+#define SPMV_TRSV_UPPER 1
+#define SPMV_TRSV_DIAG_NONUNIT 0
+#define SPMV_TRSV_DIAG_UNIT 1
+typedef struct spmv_trsv_stats {
+    uint64_t n, nr_nzeros;        /* stored entries of the triangle, diagonal included (DIAG_UNIT: the
+                                     ignored diagonal entries are not counted) */
+    uint64_t nr_levels;           /* dependency levels */
+    uint64_t nr_launches;         /* kernels one solve enqueues */
+    uint64_t nr_chain_levels;     /* levels solved inside single-workgroup chain launches */
+    uint64_t max_level_rows;
+    uint64_t device_bytes;
+    int32_t  device, uplo, diag, reserved;
+} spmv_trsv_stats;
+int  spmv_trsv_create_device(spmv_trsv **t, int device, int uplo, int diag, uint32_t n,
+                             uint32_t nr_nzeros, const IndexType *d_row_ptr, const IndexType *d_col_ind,
+                             const ValueType *d_values, void *stream);
+int  spmv_trsv_create_host(spmv_trsv **t, int device, int uplo, int diag, const csr_matrix *matrix);
+int  spmv_trsv_solve(const spmv_trsv *t, const ValueType *d_b, ValueType *d_x, void *stream);
+int  spmv_trsv_get_stats(const spmv_trsv *t, spmv_trsv_stats *stats);
+void spmv_trsv_destroy(spmv_trsv *t);
+
 /* ---------------- synthetic inputs (bench/test infrastructure) ---------------- */
 /* Banded: n x n, `width` non-zeros per row, columns [clamp(i - width/2, 0, n - width), +width),
  * values U(-1,1) from splitmix64(seed). Writes d_row_ptr[n+1], d_col[n*width], d_val. */

@@ -1,6 +1,7 @@
-// Host-only internals of libspmv_hw (no HIP): what host.cpp, layout.cpp and reader.cpp share with the
-// rest of the library. tests/sanitize/Makefile compiles these three sources with g++ -fsanitize=... into a
-// host-only check program, so nothing here may need the HIP headers.
+// Host-only internals of libspmv_hw (no HIP): what host.cpp, layout.cpp, trsv_plan.cpp and reader.cpp share
+// with the rest of the library. tests/sanitize/Makefile compiles host.cpp, layout.cpp and reader.cpp with g++
+// -fsanitize=... into a host-only check program (tests/trsv_host does the same for trsv_plan.cpp), so nothing
+// here may need the HIP headers.
 #pragma once
 
 #include <algorithm>
@@ -147,6 +148,47 @@ struct tile_plan {
 // Returns 0, or 1 with the error "too many non-empty rows for the tile table" or "internal:
 // unterminated row crossing".
 int plan_tiles(const IndexType *h_rp, IndexType n, uint64_t nnz, bool has_empty, tile_plan &out);
+
+// Host planner of the sparse triangular solve (trsv_plan.cpp): the dependency levels of
+// the `uplo` triangle of a square CSR matrix, the launch list one solve walks, and the permuted layout
+// trsv.hip uploads. No HIP and no environment.
+constexpr uint32_t kTrsvChainRows = 1024;  // a level of at most this many rows is narrow: runs of narrow
+                                           // levels share one single-workgroup launch (one row per thread)
+constexpr uint32_t kTrsvLongRow = 32;      // a row with more off-diagonal entries than this gets a whole wave
+struct trsv_launch {
+    uint32_t chain;                    // 1: k_trsv_chain over levels [level_begin, level_end); 0: k_trsv_level
+    uint32_t level_begin, level_end;   // (a wide launch holds exactly one level)
+};
+struct trsv_plan {
+    std::vector<uint32_t> level;      // dependency level of every row [n]
+    std::vector<uint32_t> perm;       // the rows sorted by (level, row) [n]
+    std::vector<uint32_t> level_ptr;  // first position of each level in perm / order [levels + 1]
+    std::vector<uint32_t> order;      // the rows as the kernels take them: by level, inside a level the short
+                                      // rows (by row index) and then the long ones (by row index) [n]
+    std::vector<uint32_t> long_ptr;   // first position in `order` of each level's long rows [levels]
+    std::vector<uint32_t> offdiag;    // in-triangle off-diagonal entries of every row [n]
+    std::vector<trsv_launch> launches;
+    int64_t missing_diag_row = -1;    // first row (lowest index) without a stored diagonal; -1: none
+    int64_t bad_col_row = -1;         // first row holding a column index >= n; -1: none (the plan is valid)
+    uint64_t tri_nnz = 0;             // entries the solve uses: off-diagonal ones, and the stored diagonal
+                                      // entries unless the diagonal is unit
+    uint64_t nr_chain_levels = 0, max_level_rows = 0;
+    uint32_t levels() const { return level_ptr.empty() ? 0 : (uint32_t)level_ptr.size() - 1; }
+};
+// One pass over the rows (ascending for SPMV_TRSV_LOWER, descending for SPMV_TRSV_UPPER): a row without
+// in-triangle off-diagonal entries has level 0, any other 1 + the highest level among their columns.
+// rp is rebased to 0; the columns of a row need not be sorted and may repeat.
+void plan_trsv(IndexType n, const IndexType *rp, const IndexType *col, int uplo, int diag, trsv_plan &out);
+// The layout of a valid plan: the off-diagonal triangle as CSR over the positions of plan.order (the
+// entries of a row keep their CSR order, columns stay matrix columns = indices into x), and the
+// diagonal of each position (duplicates added in CSR order; 1 when the diagonal is unit).
+struct trsv_layout {
+    std::vector<uint32_t> rp;  // [n + 1]
+    std::vector<IndexType> col;
+    std::vector<ValueType> val, diag;
+};
+void build_trsv_layout(IndexType n, const IndexType *rp, const IndexType *col, const ValueType *val, int uplo,
+                       int diag, const trsv_plan &plan, trsv_layout &out);
 
 // wall clock in microseconds (util.cpp:3-8)
 double timestamp_us();

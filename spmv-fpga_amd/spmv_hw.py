@@ -108,6 +108,17 @@ class spmv_multi_stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class spmv_trsv_stats(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint64), ("nr_nzeros", ctypes.c_uint64), ("nr_levels", ctypes.c_uint64),
+                ("nr_launches", ctypes.c_uint64), ("nr_chain_levels", ctypes.c_uint64),
+                ("max_level_rows", ctypes.c_uint64), ("device_bytes", ctypes.c_uint64),
+                ("device", ctypes.c_int32), ("uplo", ctypes.c_int32), ("diag", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 # every symbol include/csr_hw_wrapper.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "create_csr_hw_matrix", "create_csr_hw_y_vector", "create_csr_hw_x_vector", "spmv_hw",
@@ -120,6 +131,7 @@ EXPORTS = [
     "spmv_multi_destroy", "spmv_multi_get_plan_stats",
     "spmv_plan_create_device_op", "spmv_plan_create_host_op", "spmv_plan_get_op", "spmv_csr_transpose_device",
     "spmv_multi_create_device_op", "spmv_multi_create_host_op",
+    "spmv_trsv_create_device", "spmv_trsv_create_host", "spmv_trsv_solve", "spmv_trsv_get_stats", "spmv_trsv_destroy",
     "spmv_gen_banded", "spmv_gen_powerlaw_row_ptr", "spmv_gen_fill", "spmv_gen_vector",
     "spmv_read_csr_header", "spmv_read_csr_matrix", "spmv_read_csr", "spmv_free_csr",
     "spmv_mgpu_create", "spmv_mgpu_set_x", "spmv_mgpu_run", "spmv_mgpu_get_y", "spmv_mgpu_get_timing",
@@ -129,6 +141,8 @@ EXPORTS = [
 ]
 
 OP_N, OP_T = 0, 1  # include/csr_hw_wrapper.h SPMV_OP_*
+TRSV_LOWER, TRSV_UPPER = 0, 1  # include/csr_hw_wrapper.h SPMV_TRSV_*
+TRSV_DIAG_NONUNIT, TRSV_DIAG_UNIT = 0, 1
 MGPU_GATHER, MGPU_REDUCE, MGPU_ALLGATHER = 0, 1, 2  # include/csr_hw_wrapper.h SPMV_MGPU_*
 # spmv_xop kinds and buffers (include/csr_hw_wrapper.h SPMV_XOP_* / SPMV_XBUF_*)
 XOP_ZERO, XOP_COMPUTE, XOP_SEND, XOP_RECV, XOP_REDUCE, XOP_BCAST = range(6)
@@ -206,6 +220,13 @@ class Lib:
             "spmv_multi_create_host_op": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int,
                                                          ctypes.POINTER(self.csr_matrix), IndexType, IndexType,
                                                          ctypes.c_int]),
+            "spmv_trsv_create_device": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       IndexType, IndexType, vp, vp, vp, vp]),
+            "spmv_trsv_create_host": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.POINTER(self.csr_matrix)]),
+            "spmv_trsv_solve": (ctypes.c_int, [vp, vp, vp, vp]),
+            "spmv_trsv_get_stats": (ctypes.c_int, [vp, ctypes.POINTER(spmv_trsv_stats)]),
+            "spmv_trsv_destroy": (None, [vp]),
             "spmv_partition_rows": (ctypes.c_int, [up, IndexType, ctypes.c_int, up]),
             "spmv_gen_banded": (ctypes.c_int, [IndexType, IndexType, ctypes.c_uint64, vp, vp, vp, vp]),
             "spmv_gen_powerlaw_row_ptr": (ctypes.c_int, [IndexType, ctypes.c_uint64, IndexType, ctypes.c_uint64,
@@ -512,6 +533,63 @@ class MultiPlan:
     def destroy(self) -> None:
         if self.h:
             self.lib.L.spmv_multi_destroy(self.h)
+            self.h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class TriSolve:
+    """T x = b for the lower or upper triangle T of a square CSR matrix (spmv_trsv_*,
+    include/csr_hw_wrapper.h Part 5): entries on the other side of the diagonal are ignored, so a
+    full symmetric A gives both Gauss-Seidel sweeps. solve() overwrites x (x may be b itself), is
+    asynchronous on the stream and bitwise reproducible. stats(): levels, launches per solve, ..."""
+
+    def __init__(self, lib: Lib, handle: ctypes.c_void_p, n: int):
+        self.lib = lib
+        self.h = handle
+        self.n = int(n)
+
+    @classmethod
+    def from_device(cls, lib: Lib, row_ptr, col, val, n: int, lower: bool = True, unit_diag: bool = False,
+                    device: int = 0, stream=None):
+        """row_ptr/col/val: torch tensors on `device` (uint32 viewed as int32, values of lib.dtype);
+        row_ptr holds n + 1 entries and may start at any offset. The analysis runs on the host:
+        col and val are copied back once."""
+        h = ctypes.c_void_p()
+        nnz = int(row_ptr[n].item()) - int(row_ptr[0].item()) if n > 0 else 0
+        lib._ok(lib.L.spmv_trsv_create_device(ctypes.byref(h), device, TRSV_LOWER if lower else TRSV_UPPER,
+                                              TRSV_DIAG_UNIT if unit_diag else TRSV_DIAG_NONUNIT, int(n),
+                                              nnz & 0xFFFFFFFF, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(),
+                                              _stream_ptr(stream)), "spmv_trsv_create_device")
+        return cls(lib, h, n)
+
+    @classmethod
+    def from_host(cls, lib: Lib, matrix, lower: bool = True, unit_diag: bool = False, device: int = 0):
+        h = ctypes.c_void_p()
+        lib._ok(lib.L.spmv_trsv_create_host(ctypes.byref(h), device, TRSV_LOWER if lower else TRSV_UPPER,
+                                            TRSV_DIAG_UNIT if unit_diag else TRSV_DIAG_NONUNIT, ctypes.byref(matrix)),
+                "spmv_trsv_create_host")
+        return cls(lib, h, int(matrix.nr_rows))
+
+    def solve(self, b, x, stream=None) -> None:
+        for name, t in (("b", b), ("x", x)):
+            if t.numel() != self.n or t.dtype != _torch_dtype(self.lib.dtype) or not t.is_contiguous():
+                raise ValueError(f"TriSolve.solve: {name} must be a contiguous {self.lib.dtype} tensor of {self.n} values")
+        self.lib._ok(self.lib.L.spmv_trsv_solve(self.h, b.data_ptr(), x.data_ptr(), _stream_ptr(stream)),
+                     "spmv_trsv_solve")
+
+    def stats(self) -> dict:
+        st = spmv_trsv_stats()
+        self.lib._ok(self.lib.L.spmv_trsv_get_stats(self.h, ctypes.byref(st)), "spmv_trsv_get_stats")
+        return st.as_dict()
+
+    def destroy(self) -> None:
+        if self.h:
+            self.lib.L.spmv_trsv_destroy(self.h)
             self.h = None
 
     def __del__(self):  # pragma: no cover
