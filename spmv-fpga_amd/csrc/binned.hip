@@ -22,15 +22,15 @@
 // group of PER entries is one 16-byte load; each window's range starts on a 128-entry boundary
 // (whole 128-byte lines for pass 1's wave loads and stores). Pad (and escape) entries: value 0,
 // column offset kBinSent, for which pass 1 writes an exact +0 product (0 * x would be NaN for
-// a non-finite x); row offset 0 / delta 0 (or 255 for an escape).
-//   d_b_val   V[ent_pad]    values, window-major
-//   d_b_colw  u16[ent_pad]  column - window base
-//   d_b_rowp  u16[ent_pad]  row - panel base, or (b_delta: segments sorted by row) u8 deltas
+// a non-finite x); row offset 0 / delta 0 (or 255 for an escape). In binned_state (and panels):
+//   val       V[ent_pad]    values, window-major
+//   colw      u16[ent_pad]  column - window base
+//   rowp      u16[ent_pad]  row - panel base, or (delta: segments sorted by row) u8 deltas
 //             from the previous entry of the segment (the first from row 0), gaps above 255
 //             bridged by escape entries (delta 255, product 0)
-//   d_b_prod  V[ent_pad]    products (scratch written by pass 1, read by pass 2)
-//   d_b_seg   u64[nwin * npan + 1]  padded segment offsets, index w * npan + p
-//   d_b_ub    u64[nunits + 1], d_b_uwin u32[nunits]: pass-1 work units (a window, or a piece of
+//   prod      V[ent_pad]    products (scratch written by pass 1, read by pass 2)
+//   seg       u64[nwin * npan + 1]  padded segment offsets, index w * npan + p
+//   ub        u64[nunits + 1], uwin u32[nunits]: pass-1 work units (a window, or a piece of
 //             a window holding > 2x the mean entries)
 // Bytes per non-zero: fp32 4 + 2 read, 4 written, 4 + 2 (1 with deltas) read = 16 (15); fp64
 // 28 (27). Both passes are
@@ -509,13 +509,15 @@ __global__ void k_bin_pad(uint64_t nseg, const uint64_t *__restrict__ seg, const
 
 hipError_t launch_binned(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm)
 {
+    const binned_state &w = p.binned;
+    const panels_state &pn = p.panels;
     if (p.nr_rows == 0)
         return hipSuccess;
     constexpr uint64_t PERV = 16 / sizeof(ValueType);
     // variant 7: mirrored products (k_bin_mul); the index of the last product vector
-    const uint64_t mirror = p.variant == 7 ? std::max<uint64_t>(p.ent_pad, PERV) - PERV : 0;
-    if (p.b_nunits) {
-        const size_t lds1 = size_t(std::max(p.b_W, p.b_W1)) * sizeof(ValueType);
+    const uint64_t mirror = p.variant == 7 ? std::max<uint64_t>(pn.ent_pad, PERV) - PERV : 0;
+    if (w.nunits) {
+        const size_t lds1 = size_t(std::max(w.W, w.W1)) * sizeof(ValueType);
         const bool al = (reinterpret_cast<uintptr_t>(d_x) & 15u) == 0;
         // pass-1 cache policy: temporal product stores when the products fit well within
         // reach of the 256 MB MALL (fp32 10M/160M: 640 MB, 0.460 vs 0.487 ms; fp64 1.28 GB:
@@ -523,61 +525,61 @@ hipError_t launch_binned(const spmv_plan &p, const ValueType *d_x, ValueType *d_
         // non-temporal stores
         const int pol = p.variant >= 3 && p.variant <= 5 ? p.variant - 2
                         : p.variant == 6                ? 0
-                                                        : (p.b_prod_temporal ? 1 : 0);
+                                                        : (w.prod_temporal ? 1 : 0);
         if (pol && al) {
 #define BINPOL(P)                                                                                          \
-    launch_or_warm(warm, k_bin_mul<ValueType, true, P>, dim3((unsigned)p.b_nunits), dim3(kBinT), lds1, s, d_x, \
-                   (uint32_t)p.nr_cols, p.b_W, p.b_W1, p.d_b_ub, p.d_b_uwin, p.d_b_colw, p.d_b_val, p.d_b_prod, mirror)
+    launch_or_warm(warm, k_bin_mul<ValueType, true, P>, dim3((unsigned)w.nunits), dim3(kBinT), lds1, s, d_x, \
+                   (uint32_t)p.nr_cols, w.W, w.W1, w.ub.get(), w.uwin.get(), w.colw.get(), w.val.get(), w.prod, mirror)
             if (pol == 1) BINPOL(1); else if (pol == 2) BINPOL(2); else BINPOL(3);
 #undef BINPOL
         } else if (al || warm)
-            launch_or_warm(warm, k_bin_mul<ValueType, true>, dim3((unsigned)p.b_nunits), dim3(kBinT), lds1, s, d_x,
-                           (uint32_t)p.nr_cols, p.b_W, p.b_W1, p.d_b_ub, p.d_b_uwin, p.d_b_colw, p.d_b_val, p.d_b_prod, mirror);
+            launch_or_warm(warm, k_bin_mul<ValueType, true>, dim3((unsigned)w.nunits), dim3(kBinT), lds1, s, d_x,
+                           (uint32_t)p.nr_cols, w.W, w.W1, w.ub.get(), w.uwin.get(), w.colw.get(), w.val.get(), w.prod, mirror);
         if (!al || warm)
-            launch_or_warm(warm, k_bin_mul<ValueType, false>, dim3((unsigned)p.b_nunits), dim3(kBinT), lds1, s, d_x,
-                           (uint32_t)p.nr_cols, p.b_W, p.b_W1, p.d_b_ub, p.d_b_uwin, p.d_b_colw, p.d_b_val, p.d_b_prod, mirror);
+            launch_or_warm(warm, k_bin_mul<ValueType, false>, dim3((unsigned)w.nunits), dim3(kBinT), lds1, s, d_x,
+                           (uint32_t)p.nr_cols, w.W, w.W1, w.ub.get(), w.uwin.get(), w.colw.get(), w.val.get(), w.prod, mirror);
     }
-    const size_t lds2 = (size_t(p.panel_rmax) + 1) * sizeof(double);
+    const size_t lds2 = (size_t(pn.rmax) + 1) * sizeof(double);
     // variants 1 / 2 (tests): segment offsets rebased past 2^31 / 2^32, the product and row arrays
     // rebased the other way, so pass 2 touches the same addresses through 64-bit offsets whose low
     // word has bit 31 set (spmv_plan_set_variant)
-    const uint64_t base = p.d_b_seg_hi ? p.b_seg_base : 0;
-    const uint64_t *seg = p.d_b_seg_hi ? p.d_b_seg_hi : p.d_b_seg;
+    const uint64_t base = w.seg_hi.get() ? w.seg_base : 0;
+    const uint64_t *seg = w.seg_hi.get() ? w.seg_hi.get() : w.seg.get();
     const ValueType *prod = reinterpret_cast<const ValueType *>(
-        reinterpret_cast<uintptr_t>(p.d_b_prod) - base * sizeof(ValueType));
-    const void *rowp = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(p.d_b_rowp) -
-                                                      base * (p.b_delta ? 1 : 2));
+        reinterpret_cast<uintptr_t>(w.prod) - base * sizeof(ValueType));
+    const void *rowp = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(w.rowp.p) -
+                                                      base * (w.delta ? 1 : 2));
     // pass 2 sees offsets ld + base against prod - base: the mirrored index is mirror + 2 base - ld
     const uint64_t mirror2 = mirror ? mirror + 2 * base : 0;
 #ifdef SPMV_ABLATIONS
-    if (p.b_delta && (p.variant == 51 || p.variant == 52)) {
+    if (w.delta && (p.variant == 51 || p.variant == 52)) {
         if (p.variant == 51)
-            launch_or_warm(warm, k_bin_acc<ValueType, true, 1>, dim3((unsigned)p.npanels), dim3(kBinT), lds2, s, prod,
-                           rowp, seg, p.d_panel_row, p.b_nwin, (uint32_t)p.npanels, p.panel_rmax + 1, d_y, mirror2);
+            launch_or_warm(warm, k_bin_acc<ValueType, true, 1>, dim3((unsigned)pn.npanels), dim3(kBinT), lds2, s, prod,
+                           rowp, seg, pn.row.get(), w.nwin, (uint32_t)pn.npanels, pn.rmax + 1, d_y, mirror2);
         else
-            launch_or_warm(warm, k_bin_acc<ValueType, true, 2>, dim3((unsigned)p.npanels), dim3(kBinT), lds2, s, prod,
-                           rowp, seg, p.d_panel_row, p.b_nwin, (uint32_t)p.npanels, p.panel_rmax + 1, d_y, mirror2);
+            launch_or_warm(warm, k_bin_acc<ValueType, true, 2>, dim3((unsigned)pn.npanels), dim3(kBinT), lds2, s, prod,
+                           rowp, seg, pn.row.get(), w.nwin, (uint32_t)pn.npanels, pn.rmax + 1, d_y, mirror2);
         return hipGetLastError();
     }
 #endif
-    // spmv_hw's streamed copy-back: the flagged pass 2 (sweep_can_flag_panels)
-    if (p.y_flag || warm) {
-        if (p.b_delta)
-            launch_or_warm(warm, k_bin_acc<ValueType, true, 0, uint32_t *, uint32_t>, dim3((unsigned)p.npanels),
-                           dim3(kBinT), lds2, s, prod, rowp, seg, p.d_panel_row, p.b_nwin, (uint32_t)p.npanels,
-                           p.panel_rmax + 1, d_y, mirror2, p.y_flag, p.y_epoch);
+    // spmv_hw's streamed copy-back: the flagged pass 2 (binned_flags_panels)
+    if (p.release.y_flag || warm) {
+        if (w.delta)
+            launch_or_warm(warm, k_bin_acc<ValueType, true, 0, uint32_t *, uint32_t>, dim3((unsigned)pn.npanels),
+                           dim3(kBinT), lds2, s, prod, rowp, seg, pn.row.get(), w.nwin, (uint32_t)pn.npanels,
+                           pn.rmax + 1, d_y, mirror2, p.release.y_flag, p.release.y_epoch);
         else
-            launch_or_warm(warm, k_bin_acc<ValueType, false, 0, uint32_t *, uint32_t>, dim3((unsigned)p.npanels),
-                           dim3(kBinT), lds2, s, prod, rowp, seg, p.d_panel_row, p.b_nwin, (uint32_t)p.npanels,
-                           p.panel_rmax + 1, d_y, mirror2, p.y_flag, p.y_epoch);
+            launch_or_warm(warm, k_bin_acc<ValueType, false, 0, uint32_t *, uint32_t>, dim3((unsigned)pn.npanels),
+                           dim3(kBinT), lds2, s, prod, rowp, seg, pn.row.get(), w.nwin, (uint32_t)pn.npanels,
+                           pn.rmax + 1, d_y, mirror2, p.release.y_flag, p.release.y_epoch);
     }
-    if (!p.y_flag) {
-        if (p.b_delta)
-            launch_or_warm(warm, k_bin_acc<ValueType, true>, dim3((unsigned)p.npanels), dim3(kBinT), lds2, s, prod,
-                           rowp, seg, p.d_panel_row, p.b_nwin, (uint32_t)p.npanels, p.panel_rmax + 1, d_y, mirror2);
+    if (!p.release.y_flag) {
+        if (w.delta)
+            launch_or_warm(warm, k_bin_acc<ValueType, true>, dim3((unsigned)pn.npanels), dim3(kBinT), lds2, s, prod,
+                           rowp, seg, pn.row.get(), w.nwin, (uint32_t)pn.npanels, pn.rmax + 1, d_y, mirror2);
         else
-            launch_or_warm(warm, k_bin_acc<ValueType, false>, dim3((unsigned)p.npanels), dim3(kBinT), lds2, s, prod,
-                           rowp, seg, p.d_panel_row, p.b_nwin, (uint32_t)p.npanels, p.panel_rmax + 1, d_y, mirror2);
+            launch_or_warm(warm, k_bin_acc<ValueType, false>, dim3((unsigned)pn.npanels), dim3(kBinT), lds2, s, prod,
+                           rowp, seg, pn.row.get(), w.nwin, (uint32_t)pn.npanels, pn.rmax + 1, d_y, mirror2);
     }
     return hipGetLastError();
 }
@@ -607,17 +609,17 @@ static int bin_check_skew(const spmv_plan &p, const IndexType *h_rp, const std::
     // address each, serialised (2M rows of ~16 plus two rows of 2M entries, fp32: 2.60 ms here
     // against 0.42 ms for the sweep, which cuts such panels into pieces). The automatic choice
     // then takes the sweep.
-    if (p.bin_skew_limit > 0.0 && P > 1 && double(emax) > p.bin_skew_limit * double(nnz) / P) {
+    if (p.binned.skew_limit > 0.0 && P > 1 && double(emax) > p.binned.skew_limit * double(nnz) / P) {
         set_error("build_binned: a panel holds long rows (skewed)");
         return 2;
     }
     // Balanced panels still let a row of up to ~2x the mean panel entries pass the test above;
     // its adds all land on one LDS address. The longest row is checked on its own.
-    if (p.bin_row_limit > 0.0 && P > 0) {
+    if (p.binned.row_limit > 0.0 && P > 0) {
         uint64_t lmax = 0;
         for (IndexType r = 0; r < p.nr_rows; ++r)
             lmax = std::max<uint64_t>(lmax, uint64_t(h_rp[r + 1]) - h_rp[r]);
-        if (double(lmax) > p.bin_row_limit * double(nnz) / P) {
+        if (double(lmax) > p.binned.row_limit * double(nnz) / P) {
             set_error("build_binned: a row holds " + std::to_string(lmax) + " entries (long row)");
             return 2;
         }
@@ -640,8 +642,8 @@ static int bin_count(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col
     SPMV_BUILD_TRY(hipMemcpyAsync(d_rp, h_rp, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
     SPMV_BUILD_TRY(t.key.alloc(nnz));
     SPMV_BUILD_TRY(t.rowp.alloc(nnz));
-    SPMV_BUILD_TRY(launch_items(k_bin_keys, nnz, 256, s, d_rp.get(), n, d_col_src, nnz, p.d_panel_row,
-                                (uint32_t)p.npanels, p.b_W, p.b_W1, t.key.get(), t.rowp.get(), t.cnt.get()));
+    SPMV_BUILD_TRY(launch_items(k_bin_keys, nnz, 256, s, d_rp.get(), n, d_col_src, nnz, p.panels.row.get(),
+                                (uint32_t)p.panels.npanels, p.binned.W, p.binned.W1, t.key.get(), t.rowp.get(), t.cnt.get()));
     SPMV_BUILD_TRY(hipMemcpyAsync(cnt.data(), t.cnt, nseg * 4, hipMemcpyDeviceToHost, s));
     SPMV_BUILD_TRY(hipStreamSynchronize(s));
     return 0;
@@ -714,24 +716,26 @@ static int bin_sort_rows(spmv_plan &p, hipStream_t s, bool always, const std::ve
 static int bin_scatter(spmv_plan &p, const IndexType *d_col_src, const ValueType *d_val_src, hipStream_t s,
                        const std::vector<uint32_t> &esc, bin_scratch &t)
 {
+    binned_state &w = p.binned;
+    panels_state &pn = p.panels;
     const uint64_t nnz = p.nnz, nseg = esc.size();
-    const uint32_t P = (uint32_t)p.npanels;
-    if (p.b_delta) {
+    const uint32_t P = (uint32_t)pn.npanels;
+    if (w.delta) {
         SPMV_BUILD_TRY(launch_items(k_bin_scatter_delta<ValueType>, nnz, 256, s, t.k64s.get(), t.idxs.get(),
-                                    t.pscan.get(), t.soff.get(), nnz, P, p.b_W, p.b_W1, d_col_src, d_val_src, p.d_b_seg,
-                                    p.d_b_val, p.d_b_colw, reinterpret_cast<uint8_t *>(p.d_b_rowp)));
+                                    t.pscan.get(), t.soff.get(), nnz, P, w.W, w.W1, d_col_src, d_val_src, w.seg.get(),
+                                    w.val.get(), w.colw.get(), reinterpret_cast<uint8_t *>(w.rowp.p)));
         SPMV_BUILD_TRY(hipMemcpyAsync(t.esc, esc.data(), nseg * 4, hipMemcpyHostToDevice, s));
-        SPMV_BUILD_TRY(launch_items(k_bin_pad<ValueType, true>, nseg, 256, s, nseg, p.d_b_seg, t.cnt.get(), t.esc.get(),
-                                    p.d_b_val, p.d_b_colw, (void *)p.d_b_rowp));
+        SPMV_BUILD_TRY(launch_items(k_bin_pad<ValueType, true>, nseg, 256, s, nseg, w.seg.get(), t.cnt.get(), t.esc.get(),
+                                    w.val.get(), w.colw.get(), (void *)w.rowp.p));
     } else {
         device_buf<uint32_t> cur;
         SPMV_BUILD_TRY(cur.alloc(nseg));
         SPMV_BUILD_TRY(hipMemsetAsync(cur, 0, nseg * 4, s));
         SPMV_BUILD_TRY(launch_items(k_bin_scatter<ValueType>, nnz, 256, s, t.key.get(), t.rowp.get(), d_col_src, d_val_src,
-                                    nnz, P, p.b_W, p.b_W1, p.d_b_seg, cur.get(), p.d_b_val, p.d_b_colw,
-                                    reinterpret_cast<uint16_t *>(p.d_b_rowp)));
-        SPMV_BUILD_TRY(launch_items(k_bin_pad<ValueType, false>, nseg, 256, s, nseg, p.d_b_seg, t.cnt.get(),
-                                    (const uint32_t *)nullptr, p.d_b_val, p.d_b_colw, (void *)p.d_b_rowp));
+                                    nnz, P, w.W, w.W1, w.seg.get(), cur.get(), w.val.get(), w.colw.get(),
+                                    reinterpret_cast<uint16_t *>(w.rowp.p)));
+        SPMV_BUILD_TRY(launch_items(k_bin_pad<ValueType, false>, nseg, 256, s, nseg, w.seg.get(), t.cnt.get(),
+                                    (const uint32_t *)nullptr, w.val.get(), w.colw.get(), (void *)w.rowp.p));
         SPMV_BUILD_TRY(hipStreamSynchronize(s));  // cur goes with the scope
     }
     return 0;
@@ -745,6 +749,8 @@ static int bin_scatter(spmv_plan &p, const IndexType *d_col_src, const ValueType
 int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src, const ValueType *d_val_src,
                  hipStream_t s)
 {
+    binned_state &w = p.binned;
+    panels_state &pn = p.panels;
     const IndexType n = p.nr_rows;
     const uint64_t nnz = p.nnz;
     const uint64_t cus = device_cu_count(p.device);
@@ -773,15 +779,15 @@ int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
         set_error("build_binned: too many (window, panel) segments");
         return 2;
     }
-    p.npanels = P;
-    p.panel_rmax = 0;
+    pn.npanels = P;
+    pn.rmax = 0;
     for (uint32_t q = 0; q < P; ++q)
-        p.panel_rmax = std::max(p.panel_rmax, prow[q + 1] - prow[q]);
-    p.b_nwin = (uint32_t)win.nwin;
-    p.b_W = (uint32_t)win.W0;
-    p.b_W1 = (uint32_t)win.W1;
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_panel_row, (P + 1) * 4));
-    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_panel_row, prow.data(), (P + 1) * 4, hipMemcpyHostToDevice, s));
+        pn.rmax = std::max(pn.rmax, prow[q + 1] - prow[q]);
+    w.nwin = (uint32_t)win.nwin;
+    w.W = (uint32_t)win.W0;
+    w.W1 = (uint32_t)win.W1;
+    SPMV_BUILD_TRY(pn.row.alloc(P + 1));
+    SPMV_BUILD_TRY(hipMemcpyAsync(pn.row.get(), prow.data(), (P + 1) * 4, hipMemcpyHostToDevice, s));
 
     bin_scratch t;
     std::vector<uint32_t> cnt(nseg, 0), esc(nseg, 0);
@@ -797,32 +803,32 @@ int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
     if (nnz && !never)
         if (int rc = bin_sort_rows(p, s, always, cnt, t, esc, &delta))
             return rc;
-    p.b_delta = delta;
+    w.delta = delta;
     bin_units bu;
     plan_bin_units(cnt, esc, win.nwin, P, cus, bu);
     const uint64_t ent_pad = bu.seg[nseg];
-    p.ent_pad = ent_pad;
-    p.b_prod_temporal = ent_pad * sizeof(ValueType) <= (1ull << 30);
-    p.b_nunits = bu.uwin.size();
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_seg, (nseg + 1) * 8));
-    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_b_seg, bu.seg.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, s));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_ub, bu.ub.size() * 8));
-    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_b_ub, bu.ub.data(), bu.ub.size() * 8, hipMemcpyHostToDevice, s));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_uwin, std::max<size_t>(bu.uwin.size(), 1) * 4));
+    pn.ent_pad = ent_pad;
+    w.prod_temporal = ent_pad * sizeof(ValueType) <= (1ull << 30);
+    w.nunits = bu.uwin.size();
+    SPMV_BUILD_TRY(w.seg.alloc(nseg + 1));
+    SPMV_BUILD_TRY(hipMemcpyAsync(w.seg.get(), bu.seg.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(w.ub.alloc(bu.ub.size()));
+    SPMV_BUILD_TRY(hipMemcpyAsync(w.ub.get(), bu.ub.data(), bu.ub.size() * 8, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(w.uwin.alloc(std::max<size_t>(bu.uwin.size(), 1)));
     if (!bu.uwin.empty())
-        SPMV_BUILD_TRY(hipMemcpyAsync(p.d_b_uwin, bu.uwin.data(), bu.uwin.size() * 4, hipMemcpyHostToDevice, s));
+        SPMV_BUILD_TRY(hipMemcpyAsync(w.uwin.get(), bu.uwin.data(), bu.uwin.size() * 4, hipMemcpyHostToDevice, s));
     const uint64_t alloc = std::max<uint64_t>(ent_pad, kBinPer);
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_val, alloc * sizeof(ValueType)));
+    SPMV_BUILD_TRY(w.val.alloc(alloc));
     {
         // env SPMV_BIN_PROD_SKEW=bytes (measurement): the products start that far (a multiple of
         // 256 B) into their allocation, shifting their address bits against the entry arrays'
         const char *sk = ablation_env("SPMV_BIN_PROD_SKEW");
         const uint64_t skew = sk ? (uint64_t)std::strtoull(sk, nullptr, 10) / 256 * 256 : 0;
-        SPMV_BUILD_TRY(hipMalloc(&p.d_b_prod_alloc, alloc * sizeof(ValueType) + skew));
-        p.d_b_prod = reinterpret_cast<ValueType *>(static_cast<unsigned char *>(p.d_b_prod_alloc) + skew);
+        SPMV_BUILD_TRY(w.prod_alloc.alloc_bytes(alloc * sizeof(ValueType) + skew));
+        w.prod = reinterpret_cast<ValueType *>(static_cast<unsigned char *>(w.prod_alloc.p) + skew);
     }
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_colw, alloc * 2));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_b_rowp, alloc * (delta ? 1 : 2)));
+    SPMV_BUILD_TRY(w.colw.alloc(alloc));
+    SPMV_BUILD_TRY(w.rowp.alloc_bytes(alloc * (delta ? 1 : 2)));
     if (nnz)
         if (int rc = bin_scatter(p, d_col_src, d_val_src, s, esc, t))
             return rc;
@@ -833,12 +839,21 @@ int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
 // ---- the binned row of the layout table (spmv_internal.hpp layout_ops) ----
 static uint64_t binned_device_bytes(const spmv_plan &p)  // entries (value, 2 offsets), products, segments, units, panels
 {
-    return p.ent_pad * (2 * sizeof(ValueType) + 2 + (p.b_delta ? 1 : 2)) + (uint64_t(p.b_nwin) * p.npanels + 1) * 8 +
-           (p.b_nunits + 1) * 12 + (p.npanels + 1) * 4;
+    return p.panels.ent_pad * (2 * sizeof(ValueType) + 2 + (p.binned.delta ? 1 : 2)) + (uint64_t(p.binned.nwin) * p.panels.npanels + 1) * 8 +
+           (p.binned.nunits + 1) * 12 + (p.panels.npanels + 1) * 4;
+}
+
+// pass 2 writes whole panels (k_bin_acc), so it can flag each as it is stored (release.y_flag);
+// not its ablations
+static bool binned_flags_panels(const spmv_plan &p)
+{
+    return p.panels.npanels > 0 && p.variant != 51 && p.variant != 52;
 }
 
 static int binned_set_variant(spmv_plan &p, int variant)
 {
+    binned_state &w = p.binned;
+    panels_state &pn = p.panels;
     // 1 / 2 (tests, same y): pass 2 reads segment offsets rebased so that they straddle 2^31 /
     // 2^32 entries (prod and rowp rebased the other way: the same addresses), which drives the
     // 64-bit bound widening after readlane (k_bin_acc) without a 2^31-entry matrix
@@ -850,23 +865,22 @@ static int binned_set_variant(spmv_plan &p, int variant)
         set_error("spmv_plan_set_variant: binned variants are 0-7");
         return 1;
     }
-    if (p.d_b_seg_hi) {
+    if (w.seg_hi) {
         SPMV_TRY(hipSetDevice(p.device));
-        SPMV_TRY(hipFree(p.d_b_seg_hi));
-        p.d_b_seg_hi = nullptr;
-        p.b_seg_base = 0;
+        SPMV_TRY(w.seg_hi.release());
+        w.seg_base = 0;
     }
     if (variant == 1 || variant == 2) {
         SPMV_TRY(hipSetDevice(p.device));
-        const uint64_t nseg = uint64_t(p.b_nwin) * p.npanels + 1;
+        const uint64_t nseg = uint64_t(w.nwin) * pn.npanels + 1;
         std::vector<uint64_t> h(nseg);
-        SPMV_TRY(hipMemcpy(h.data(), p.d_b_seg, nseg * 8, hipMemcpyDeviceToHost));
+        SPMV_TRY(hipMemcpy(h.data(), w.seg.get(), nseg * 8, hipMemcpyDeviceToHost));
         const uint64_t base = (variant == 1 ? (1ull << 31) : (1ull << 32)) - h[nseg - 1] / 2;
         for (auto &v : h)
             v += base;
-        SPMV_TRY(hipMalloc((void **)&p.d_b_seg_hi, nseg * 8));
-        SPMV_TRY(hipMemcpy(p.d_b_seg_hi, h.data(), nseg * 8, hipMemcpyHostToDevice));
-        p.b_seg_base = base;
+        SPMV_TRY(w.seg_hi.alloc(nseg));
+        SPMV_TRY(hipMemcpy(w.seg_hi.get(), h.data(), nseg * 8, hipMemcpyHostToDevice));
+        w.seg_base = base;
     }
     p.variant = variant;
     return 0;
@@ -878,13 +892,13 @@ const layout_ops &binned_layout()
         "binned", "build binned layout", build_binned, kKernelSweep,  // (the segment table is too large, or skew)
         nullptr, launch_of<launch_binned>, nullptr, warm_of<launch_binned>,
         binned_device_bytes,
-        [](const spmv_plan &p) -> uint64_t { return p.npanels; },                              // units
-        [](const spmv_plan &p) -> uint64_t { return p.npanels ? p.ent_pad / p.npanels : 0; },  // unit_nnz
+        [](const spmv_plan &p) -> uint64_t { return p.panels.npanels; },                              // units
+        [](const spmv_plan &p) -> uint64_t { return p.panels.npanels ? p.panels.ent_pad / p.panels.npanels : 0; },  // unit_nnz
         one_block,
-        [](const spmv_plan &p) -> int { return p.b_delta ? 32 : 0; },  // format_bits
-        [](const spmv_plan &p) -> uint64_t { return p.ent_pad; },      // stored_entries
-        [](const spmv_plan &p) -> void * { return p.d_b_colw; },       // index_stream
-        3, {1, 2}, binned_set_variant, false,  // tune_slot, product_variants, set_variant, host_y
+        [](const spmv_plan &p) -> int { return p.binned.delta ? 32 : 0; },  // format_bits
+        [](const spmv_plan &p) -> uint64_t { return p.panels.ent_pad; },      // stored_entries
+        [](const spmv_plan &p) -> void * { return p.binned.colw.p; },     // index_stream
+        3, {1, 2}, binned_set_variant, false, binned_flags_panels,  // tune_slot, product_variants, set_variant, host_y, flags_panels
     };
     return row;
 }

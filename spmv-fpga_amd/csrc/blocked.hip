@@ -201,24 +201,27 @@ hipError_t launch_blocked(const spmv_plan &p, const ValueType *d_x, ValueType *d
 {
     if (p.nr_rows == 0)
         return hipSuccess;
-    if (p.nunits) {
-        const bool xlds = p.blocked_xlds;
-        const size_t lds = xlds ? size_t(p.fpga_width) * sizeof(ValueType) : 0;
+    const blocked_state &b = p.blocked;
+    const uint32_t W = p.csr.fpga_width;
+    if (b.nunits) {
+        const bool xlds = b.xlds;
+        const size_t lds = xlds ? size_t(W) * sizeof(ValueType) : 0;
 #define BK(VF)                                                                                                   \
     launch_or_warm(warm, xlds ? k_blocked_partials<ValueType, VF, true> : k_blocked_partials<ValueType, VF, false>, \
-                   dim3((unsigned)p.nunits), dim3(kBlockedThreads), lds, s, (const ValueType *)p.d_val,             \
-                   (const uint16_t *)p.d_colnar, (const uint32_t *)p.d_kptr, (const uint32_t *)p.d_kpos,           \
-                   (const uint32_t *)p.d_unit_panel, (const uint32_t *)p.d_unit_ent, d_x, p.nr_cols, p.fpga_width,  \
-                   p.d_bpart)
+                   dim3((unsigned)b.nunits), dim3(kBlockedThreads), lds, s, (const ValueType *)b.val.get(),        \
+                   (const uint16_t *)b.col.get(), (const uint32_t *)b.kptr.get(), (const uint32_t *)b.kpos.get(),   \
+                   (const uint32_t *)b.unit_block.get(), (const uint32_t *)b.unit_ent.get(), d_x, p.nr_cols, W,    \
+                   b.part.get())
 #ifdef SPMV_ABLATIONS
         if (p.variant == 1) {  // measurement-only ablation (tools library only): partials stored in compact-row order
-            launch_or_warm(warm, k_blocked_partials<ValueType, 1, true, 1>, dim3((unsigned)p.nunits),
-                           dim3(kBlockedThreads), lds, s, (const ValueType *)p.d_val, (const uint16_t *)p.d_colnar,
-                           (const uint32_t *)p.d_kptr, (const uint32_t *)p.d_kpos, (const uint32_t *)p.d_unit_panel,
-                           (const uint32_t *)p.d_unit_ent, d_x, p.nr_cols, p.fpga_width, p.d_bpart);
+            launch_or_warm(warm, k_blocked_partials<ValueType, 1, true, 1>, dim3((unsigned)b.nunits),
+                           dim3(kBlockedThreads), lds, s, (const ValueType *)b.val.get(), (const uint16_t *)b.col.get(),
+                           (const uint32_t *)b.kptr.get(), (const uint32_t *)b.kpos.get(),
+                           (const uint32_t *)b.unit_block.get(), (const uint32_t *)b.unit_ent.get(), d_x, p.nr_cols, W,
+                           b.part.get());
         } else
 #endif
-        switch (p.fpga_vf) {
+        switch (p.csr.fpga_vf) {
         case 8: BK(8); break;
         case 4: BK(4); break;
         case 2: BK(2); break;
@@ -226,10 +229,9 @@ hipError_t launch_blocked(const spmv_plan &p, const ValueType *d_x, ValueType *d
         }
 #undef BK
     }
-    launch_or_warm(warm, k_blocked_merge<ValueType>, dim3((unsigned)p.nchunks), dim3(kMergeThreads),
-                   size_t(kBlockedChunk) * (sizeof(ValueType) + 2), s,
-                   (const ValueType *)p.d_bpart, (const uint32_t *)p.d_rp2, (const uint16_t *)p.d_rl,
-                   (const uint32_t *)p.d_chunk_row, d_y);
+    launch_or_warm(warm, k_blocked_merge<ValueType>, dim3((unsigned)b.nchunks), dim3(kMergeThreads),
+                   size_t(kBlockedChunk) * (sizeof(ValueType) + 2), s, (const ValueType *)b.part.get(),
+                   (const uint32_t *)b.rp2.get(), (const uint16_t *)b.rl.get(), (const uint32_t *)b.chunk_row.get(), d_y);
     return hipGetLastError();
 }
 
@@ -339,7 +341,8 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         return 1;
     const IndexType n = p.nr_rows;
     const uint64_t nnz = p.nnz;
-    const uint32_t W = p.fpga_width;
+    const uint32_t W = p.csr.fpga_width;
+    blocked_state &w = p.blocked;
     if (W > 65536) {
         set_error("blocked kernel: SPMV_FPGA_BLOCK above 65536 (columns are stored as 16-bit block offsets)");
         return 1;
@@ -353,7 +356,7 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         set_error("blocked kernel: more column blocks than one row chunk holds");
         return 1;
     }
-    p.blocked_xlds = uint64_t(W) * sizeof(ValueType) <= kBlockedXLdsBytes;
+    w.xlds = uint64_t(W) * sizeof(ValueType) <= kBlockedXLdsBytes;
     uint32_t rowbits = 1;
     while (rowbits < 32 && (1ull << rowbits) < uint64_t(n))
         ++rowbits;
@@ -393,7 +396,7 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
 
     // row-major partial offsets and chunks need the per-row pair counts, so even an empty
     // matrix gets rp2 / chunk tables
-    SPMV_TRY(hipMalloc((void **)&p.d_rp2, (size_t(n) + 1) * 4));
+    SPMV_TRY(w.rp2.alloc(size_t(n) + 1));
     uint32_t *cnt = (uint32_t *)tmp.get((size_t(n) + 1) * 4);
     if (!need(cnt))
         return 1;
@@ -416,11 +419,11 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         if (!need(t))
             return 1;
         BK_TRY(hipcub::DeviceRadixSort::SortPairs(t, tb, k0, k1, i0, i1, (int)nnz, 0, (int)(rowbits + blkbits), s));
-        SPMV_TRY(hipMalloc((void **)&p.d_val, nnz * sizeof(ValueType)));
-        SPMV_TRY(hipMalloc(&p.d_colnar, nnz * 2));
+        SPMV_TRY(w.val.alloc(nnz));
+        SPMV_TRY(w.col.alloc(nnz));
         uint32_t *flag = i0, *cidx = (uint32_t *)k0;  // reuse: i0 and k0 are free after the sort
         hipLaunchKernelGGL(k_blk_gather, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, k1, i1, nnz,
-                           d_col_src, d_val_src, W, rowbits, p.d_val, (uint16_t *)p.d_colnar, flag);
+                           d_col_src, d_val_src, W, rowbits, w.val.get(), w.col.get(), flag);
         BK_TRY(hipGetLastError());
         tb = 0;
         BK_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, flag, cidx, (int)nnz, s));
@@ -433,29 +436,29 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         BK_TRY(hipMemcpyAsync(&last[1], flag + nnz - 1, 4, hipMemcpyDeviceToHost, s));
         BK_TRY(hipStreamSynchronize(s));
         K = last[0] + last[1];
-        SPMV_TRY(hipMalloc((void **)&p.d_kptr, (size_t(K) + 1) * 4));
+        SPMV_TRY(w.kptr.alloc(size_t(K) + 1));
         krow = (uint32_t *)tmp.get(size_t(K) * 4);
         kblk = (uint32_t *)tmp.get(size_t(K) * 4);
         if (!need(krow) || !need(kblk))
             return 1;
         hipLaunchKernelGGL(k_blk_compact, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, k1, flag, cidx, nnz,
-                           rowbits, p.d_kptr, krow, kblk, cnt);
+                           rowbits, w.kptr.get(), krow, kblk, cnt);
         BK_TRY(hipGetLastError());
         const uint32_t nnz32 = (uint32_t)nnz;
-        BK_TRY(hipMemcpyAsync(p.d_kptr + K, &nnz32, 4, hipMemcpyHostToDevice, s));
+        BK_TRY(hipMemcpyAsync(w.kptr.get() + K, &nnz32, 4, hipMemcpyHostToDevice, s));
     }
-    p.nkpairs = K;
+    w.nkpairs = K;
     {  // rp2 = exclusive scan of the per-row pair counts
         size_t tb = 0;
-        BK_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, p.d_rp2, (int)(n + 1), s));
+        BK_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, w.rp2.get(), (int)(n + 1), s));
         void *t = tmp.get(tb);
         if (!need(t))
             return 1;
-        BK_TRY(hipcub::DeviceScan::ExclusiveSum(t, tb, cnt, p.d_rp2, (int)(n + 1), s));
+        BK_TRY(hipcub::DeviceScan::ExclusiveSum(t, tb, cnt, w.rp2.get(), (int)(n + 1), s));
     }
     // row chunks: consecutive rows with at most kBlockedChunk partials (host, one pass)
     std::vector<uint32_t> rp2((size_t)n + 1);
-    BK_TRY(hipMemcpyAsync(rp2.data(), p.d_rp2, rp2.size() * 4, hipMemcpyDeviceToHost, s));
+    BK_TRY(hipMemcpyAsync(rp2.data(), w.rp2.get(), rp2.size() * 4, hipMemcpyDeviceToHost, s));
     BK_TRY(hipStreamSynchronize(s));
     std::vector<uint32_t> chunk_row(1, 0);
     for (IndexType r = 0; r < n;) {
@@ -468,12 +471,12 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
     }
     if (n == 0)
         chunk_row.push_back(0);
-    p.nchunks = chunk_row.size() - 1;
-    SPMV_TRY(hipMalloc((void **)&p.d_chunk_row, chunk_row.size() * 4));
-    BK_TRY(hipMemcpyAsync(p.d_chunk_row, chunk_row.data(), chunk_row.size() * 4, hipMemcpyHostToDevice, s));
-    SPMV_TRY(hipMalloc((void **)&p.d_bpart, std::max<size_t>(K, 1) * sizeof(ValueType)));
-    SPMV_TRY(hipMalloc((void **)&p.d_rl, std::max<size_t>(K, 1) * 2));
-    SPMV_TRY(hipMalloc((void **)&p.d_kpos, std::max<size_t>(K, 1) * 4));
+    w.nchunks = chunk_row.size() - 1;
+    SPMV_TRY(w.chunk_row.alloc(chunk_row.size()));
+    BK_TRY(hipMemcpyAsync(w.chunk_row.get(), chunk_row.data(), chunk_row.size() * 4, hipMemcpyHostToDevice, s));
+    SPMV_TRY(w.part.alloc(std::max<size_t>(K, 1)));
+    SPMV_TRY(w.rl.alloc(std::max<size_t>(K, 1)));
+    SPMV_TRY(w.kpos.alloc(std::max<size_t>(K, 1)));
     std::vector<uint32_t> uent, ublk;
     if (K) {
         uint32_t *ckey = (uint32_t *)tmp.get(size_t(K) * 4), *iota = (uint32_t *)tmp.get(size_t(K) * 4);
@@ -482,11 +485,11 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         if (!need(ckey) || !need(iota) || !need(ck2) || !need(ord) || !need(kb))
             return 1;
         BK_TRY(hipMemsetAsync(kb, 0xFF, (B + 1) * 4, s));
-        hipLaunchKernelGGL(k_blk_chunk_keys, dim3((K + 255) / 256), dim3(256), 0, s, krow, kblk, K, p.d_chunk_row,
-                           (uint32_t)p.nchunks, ckey, iota, kb);
+        hipLaunchKernelGGL(k_blk_chunk_keys, dim3((K + 255) / 256), dim3(256), 0, s, krow, kblk, K, w.chunk_row.get(),
+                           (uint32_t)w.nchunks, ckey, iota, kb);
         BK_TRY(hipGetLastError());
         uint32_t cbits = 1;
-        while ((1ull << cbits) < p.nchunks)
+        while ((1ull << cbits) < w.nchunks)
             ++cbits;
         size_t tb = 0;
         BK_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, ckey, ck2, iota, ord, (int)K, 0, (int)cbits, s));
@@ -494,7 +497,7 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         if (!need(t))
             return 1;
         BK_TRY(hipcub::DeviceRadixSort::SortPairs(t, tb, ckey, ck2, iota, ord, (int)K, 0, (int)cbits, s));
-        hipLaunchKernelGGL(k_blk_kpos, dim3((K + 255) / 256), dim3(256), 0, s, ord, K, p.d_kpos);
+        hipLaunchKernelGGL(k_blk_kpos, dim3((K + 255) / 256), dim3(256), 0, s, ord, K, w.kpos.get());
         BK_TRY(hipGetLastError());
         // by row (stable: blocks ascending inside a row)
         tb = 0;
@@ -503,8 +506,8 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         if (!need(t))
             return 1;
         BK_TRY(hipcub::DeviceRadixSort::SortPairs(t, tb, krow, ck2, iota, ord, (int)K, 0, (int)rowbits, s));
-        hipLaunchKernelGGL(k_blk_rl, dim3((K + 255) / 256), dim3(256), 0, s, ord, K, p.d_kpos, ckey, p.d_chunk_row,
-                           p.d_rp2, (uint16_t *)p.d_rl);
+        hipLaunchKernelGGL(k_blk_rl, dim3((K + 255) / 256), dim3(256), 0, s, ord, K, w.kpos.get(), ckey, w.chunk_row.get(),
+                           w.rp2.get(), w.rl.get());
         BK_TRY(hipGetLastError());
         // work units: each block's compact rows cut into pieces of about `target` entries
         std::vector<uint32_t> hkb(B + 1);
@@ -517,7 +520,7 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         if (!need(d_at) || !need(d_ent))
             return 1;
         BK_TRY(hipMemcpyAsync(d_at, hkb.data(), (B + 1) * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_blk_take, dim3((unsigned)((B + 1 + 255) / 256)), dim3(256), 0, s, p.d_kptr, d_at,
+        hipLaunchKernelGGL(k_blk_take, dim3((unsigned)((B + 1 + 255) / 256)), dim3(256), 0, s, w.kptr.get(), d_at,
                            (uint32_t)(B + 1), d_ent);
         BK_TRY(hipGetLastError());
         std::vector<uint32_t> hent(B + 1);
@@ -540,12 +543,12 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
         }
         uent.push_back(K);
     }
-    p.nunits = ublk.size();
-    if (p.nunits) {
-        SPMV_TRY(hipMalloc((void **)&p.d_unit_panel, ublk.size() * 4));
-        SPMV_TRY(hipMalloc((void **)&p.d_unit_ent, uent.size() * 4));
-        BK_TRY(hipMemcpyAsync(p.d_unit_panel, ublk.data(), ublk.size() * 4, hipMemcpyHostToDevice, s));
-        BK_TRY(hipMemcpyAsync(p.d_unit_ent, uent.data(), uent.size() * 4, hipMemcpyHostToDevice, s));
+    w.nunits = ublk.size();
+    if (w.nunits) {
+        SPMV_TRY(w.unit_block.alloc(ublk.size()));
+        SPMV_TRY(w.unit_ent.alloc(uent.size()));
+        BK_TRY(hipMemcpyAsync(w.unit_block.get(), ublk.data(), ublk.size() * 4, hipMemcpyHostToDevice, s));
+        BK_TRY(hipMemcpyAsync(w.unit_ent.get(), uent.data(), uent.size() * 4, hipMemcpyHostToDevice, s));
     }
     BK_TRY(hipStreamSynchronize(s));
 #undef BK_TRY
@@ -555,8 +558,8 @@ int build_blocked(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_sr
 // ---- the blocked row of the layout table (spmv_internal.hpp layout_ops) ----
 static uint64_t blocked_device_bytes(const spmv_plan &p)  // entries, kptr, kpos, rl, partials, rp2, chunks, units
 {
-    return p.nnz * (2 + sizeof(ValueType)) + (p.nkpairs + 1) * 4 + p.nkpairs * (4 + 2 + sizeof(ValueType)) +
-           (uint64_t(p.nr_rows) + 1) * 4 + (p.nchunks + 1) * 4 + p.nunits * 8 + 4;
+    return p.nnz * (2 + sizeof(ValueType)) + (p.blocked.nkpairs + 1) * 4 + p.blocked.nkpairs * (4 + 2 + sizeof(ValueType)) +
+           (uint64_t(p.nr_rows) + 1) * 4 + (p.blocked.nchunks + 1) * 4 + p.blocked.nunits * 8 + 4;
 }
 
 const layout_ops &blocked_layout()
@@ -565,13 +568,13 @@ const layout_ops &blocked_layout()
         "blocked", "build CSR layout", build_blocked, -1,
         nullptr, launch_of<launch_blocked>, nullptr, warm_of<launch_blocked>,
         blocked_device_bytes,
-        [](const spmv_plan &p) -> uint64_t { return p.nunits; },                         // units
-        [](const spmv_plan &p) -> uint64_t { return p.nunits ? p.nnz / p.nunits : 0; },  // unit_nnz
-        [](const spmv_plan &p) -> uint32_t { return (uint32_t)((uint64_t(p.nr_cols) + p.fpga_width - 1) / p.fpga_width); },
+        [](const spmv_plan &p) -> uint64_t { return p.blocked.nunits; },                         // units
+        [](const spmv_plan &p) -> uint64_t { return p.blocked.nunits ? p.nnz / p.blocked.nunits : 0; },  // unit_nnz
+        [](const spmv_plan &p) -> uint32_t { return (uint32_t)((uint64_t(p.nr_cols) + p.csr.fpga_width - 1) / p.csr.fpga_width); },
         [](const spmv_plan &) -> int { return 0; },               // format_bits
         [](const spmv_plan &p) -> uint64_t { return p.nnz; },     // stored_entries
-        [](const spmv_plan &p) -> void * { return p.d_colnar; },  // index_stream
-        -1, {0, 0}, set_tile_variant, false,  // tune_slot, product_variants, set_variant, host_y
+        [](const spmv_plan &p) -> void * { return p.blocked.col.p; },  // index_stream
+        -1, {0, 0}, set_tile_variant, false, nullptr,  // tune_slot, product_variants, set_variant, host_y, flags_panels
     };
     return row;
 }

@@ -106,7 +106,7 @@ struct hw_matrix_impl {
     ValueType *d_y = nullptr;
     ValueType *h_stage = nullptr;
     d2h_events done;  // of the y copy's pieces
-    // streamed copy-back (plans whose sweep flags each panel's y, sweep_can_flag_panels): the
+    // streamed copy-back (plans whose layout flags each panel's y, layout_ops::flags_panels): the
     // panel flags in pinned host memory, the call's epoch, the panels' row bounds and the stream
     // the pieces' copies run on while the kernel still sweeps
     uint32_t *h_flags = nullptr;
@@ -218,13 +218,20 @@ void warm_copies(ValueType *stage, const ValueType *d_src, uint64_t rows, uint64
     }
 }
 
+// the plan's layout, as the plan stands, flags each panel's y as it is stored (layout_ops)
+static bool flags_panels(const spmv_plan &pl)
+{
+    const auto can = layout_of(pl.kernel).flags_panels;
+    return can && can(pl);
+}
+
 // streamed copy-back of unit m (host merge): pinned panel flags the sweep kernel writes, the
 // panels' row bounds on the host and a copy stream (its first large copy run here, like the
 // unit stream's)
 void setup_streaming(hw_matrix_impl *m)
 {
     const spmv_plan &pl = *m->plan;
-    if (!sweep_can_flag_panels(pl) || m->row_end == m->row_begin) {
+    if (!flags_panels(pl) || m->row_end == m->row_begin) {
         if (m->copy_stream) {  // (created ahead by create_csr_hw_matrix; not needed)
             check(hipSetDevice(m->device), "hipSetDevice");
             (void)hipStreamDestroy(m->copy_stream);
@@ -233,12 +240,12 @@ void setup_streaming(hw_matrix_impl *m)
         return;
     }
     check(hipSetDevice(m->device), "hipSetDevice");
-    m->panel_rows.resize(pl.npanels + 1);
-    check(hipMemcpy(m->panel_rows.data(), pl.d_panel_row, (pl.npanels + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost),
+    m->panel_rows.resize(pl.panels.npanels + 1);
+    check(hipMemcpy(m->panel_rows.data(), pl.panels.row, (pl.panels.npanels + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost),
           "panel rows");
-    check(hipHostMalloc((void **)&m->h_flags, pl.npanels * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped),
+    check(hipHostMalloc((void **)&m->h_flags, pl.panels.npanels * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped),
           "hipHostMalloc(panel flags)");
-    std::memset(m->h_flags, 0, pl.npanels * sizeof(uint32_t));
+    std::memset(m->h_flags, 0, pl.panels.npanels * sizeof(uint32_t));
     check(hipHostGetDevicePointer((void **)&m->d_flags, m->h_flags, 0), "hipHostGetDevicePointer(panel flags)");
     if (!m->copy_stream)  // (else made by create_csr_hw_matrix while the plan built)
         check(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking), "hipStreamCreate");
@@ -412,7 +419,7 @@ double feed_pieces(std::vector<streamed_piece> &pcs, const std::vector<hw_matrix
             }
         }
         pc.t_ready = timestamp_us();
-        if (fail.empty() && m->plan->y_host) {
+        if (fail.empty() && m->plan->release.y_host) {
             // direct form: the rows are in host memory already (a piece released by the kernel's
             // end is too: the end of the kernel publishes every store at system scope)
             pc.ev = nullptr;
@@ -547,11 +554,11 @@ void spmv_hw_streamed(csr_hw_matrix **hw_matrix, int units, hw_vector_impl *x, c
             check(hipEventRecord(t_launch[u], unit_stream(u)), "hipEventRecord");
         if (++m->epoch == 0)  // (0 is the flags' initial value)
             m->epoch = 1;
-        m->plan->y_flag = m->d_flags;
-        m->plan->y_epoch = m->epoch;
-        m->plan->y_host = direct ? m->d_direct : nullptr;
+        m->plan->release.y_flag = m->d_flags;
+        m->plan->release.y_epoch = m->epoch;
+        m->plan->release.y_host = direct ? m->d_direct : nullptr;
         const int rc = spmv_plan_run(m->plan, x->per_device[m->device], m->d_y, unit_stream(u));
-        m->plan->y_flag = nullptr;
+        m->plan->release.y_flag = nullptr;
         if (rc)
             die(std::string("spmv_hw: ") + spmv_hw_last_error());
     }
@@ -568,7 +575,7 @@ void spmv_hw_streamed(csr_hw_matrix **hw_matrix, int units, hw_vector_impl *x, c
     std::thread adder([&] { landed = accumulate(parts, wait_streamed, 8); });
     const double hw_f = us.empty() ? timestamp_us() : feed_pieces(pcs, us, trace ? &seen : nullptr);
     for (hw_matrix_impl *m : us)
-        m->plan->y_host = nullptr;
+        m->plan->release.y_host = nullptr;
     const double hw_exec = (hw_f - hw_s) / 1000.0;
     std::printf("Hardware execution time : %.6f ms elapsed\n", hw_exec);
     adder.join();  // (accumulate exits the process on a failed piece)
@@ -908,7 +915,7 @@ void spmv_hw(csr_hw_matrix **hw_matrix, csr_hw_vector *hw_x, csr_vector *y_fpga,
     bool streamed = units > 0 && stream_enabled();  // (read per call, like SPMV_HW_PIPELINE)
     for (int u = 0; u < units && streamed; ++u) {
         hw_matrix_impl *m = impl(hw_matrix[u]);
-        streamed = m->row_end == m->row_begin || (m->h_flags && sweep_can_flag_panels(*m->plan));
+        streamed = m->row_end == m->row_begin || (m->h_flags && flags_panels(*m->plan));
     }
     if (streamed)
         return spmv_hw_streamed(hw_matrix, units, x, y_fpga, trace);

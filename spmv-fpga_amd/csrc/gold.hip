@@ -167,15 +167,15 @@ hipError_t launch_gold(const spmv_plan &p, const ValueType *d_x, ValueType *d_y,
         return hipSuccess;
     const uint32_t waves = (p.nr_rows + kWave - 1) / kWave;
     if (p.kernel == kKernelFpga) {
-        auto k = p.fpga_vf == 8   ? k_spmv_fpga<ValueType, 8>
-                 : p.fpga_vf == 4 ? k_spmv_fpga<ValueType, 4>
-                 : p.fpga_vf == 2 ? k_spmv_fpga<ValueType, 2>
+        auto k = p.csr.fpga_vf == 8   ? k_spmv_fpga<ValueType, 8>
+                 : p.csr.fpga_vf == 4 ? k_spmv_fpga<ValueType, 4>
+                 : p.csr.fpga_vf == 2 ? k_spmv_fpga<ValueType, 2>
                                   : k_spmv_fpga<ValueType, 1>;
-        launch_or_warm(warm, k, dim3((waves + 3) / 4), dim3(256), 0, s, p.d_rp, p.d_col, p.d_val, d_x, d_y,
-                       p.nr_rows, p.fpga_width);
+        launch_or_warm(warm, k, dim3((waves + 3) / 4), dim3(256), 0, s, p.csr.rp.get(), p.csr.col.get(),
+                       p.csr.val.get(), d_x, d_y, p.nr_rows, p.csr.fpga_width);
     } else
-        launch_or_warm(warm, k_spmv_gold<ValueType>, dim3((waves + 3) / 4), dim3(256), 0, s, p.d_rp, p.d_col,
-                       p.d_val, d_x, d_y, p.nr_rows);
+        launch_or_warm(warm, k_spmv_gold<ValueType>, dim3((waves + 3) / 4), dim3(256), 0, s, p.csr.rp.get(),
+                       p.csr.col.get(), p.csr.val.get(), d_x, d_y, p.nr_rows);
     return hipGetLastError();
 }
 
@@ -184,16 +184,16 @@ hipError_t launch_gold(const spmv_plan &p, const ValueType *d_x, ValueType *d_y,
 static int build_gold(spmv_plan &p, const IndexType *h_row_ptr, const IndexType *d_col_src,
                       const ValueType *d_val_src, hipStream_t s)
 {
-    p.nlong = 0;
+    p.csr.nlong = 0;
     for (IndexType r = 0; r < p.nr_rows; ++r)
-        p.nlong += h_row_ptr[r + 1] - h_row_ptr[r] > (IndexType)kGoldLong;
-    SPMV_TRY(hipMalloc((void **)&p.d_rp, (size_t(p.nr_rows) + 1) * sizeof(uint32_t)));
-    SPMV_TRY(hipMalloc((void **)&p.d_col, std::max<uint64_t>(p.nnz, 1) * sizeof(uint32_t)));
-    SPMV_TRY(hipMalloc((void **)&p.d_val, std::max<uint64_t>(p.nnz, 1) * sizeof(ValueType)));
-    SPMV_TRY(hipMemcpyAsync(p.d_rp, h_row_ptr, (size_t(p.nr_rows) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        p.csr.nlong += h_row_ptr[r + 1] - h_row_ptr[r] > (IndexType)kGoldLong;
+    SPMV_TRY(p.csr.rp.alloc(size_t(p.nr_rows) + 1));
+    SPMV_TRY(p.csr.col.alloc(std::max<uint64_t>(p.nnz, 1)));
+    SPMV_TRY(p.csr.val.alloc(std::max<uint64_t>(p.nnz, 1)));
+    SPMV_TRY(hipMemcpyAsync(p.csr.rp, h_row_ptr, (size_t(p.nr_rows) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     if (p.nnz) {
-        SPMV_TRY(hipMemcpyAsync(p.d_col, d_col_src, p.nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        SPMV_TRY(hipMemcpyAsync(p.d_val, d_val_src, p.nnz * sizeof(ValueType), hipMemcpyDeviceToDevice, s));
+        SPMV_TRY(hipMemcpyAsync(p.csr.col, d_col_src, p.nnz * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        SPMV_TRY(hipMemcpyAsync(p.csr.val, d_val_src, p.nnz * sizeof(ValueType), hipMemcpyDeviceToDevice, s));
     }
     SPMV_TRY(hipStreamSynchronize(s));
     return 0;
@@ -211,7 +211,7 @@ int fpga_params(spmv_plan &p)
             set_error("SPMV_FPGA_VF must be 1, 2, 4 or 8");
             return 1;
         }
-        p.fpga_vf = vf;
+        p.csr.fpga_vf = vf;
     }
     if (const char *b = std::getenv("SPMV_FPGA_BLOCK")) {
         const long w = std::atol(b);
@@ -219,7 +219,7 @@ int fpga_params(spmv_plan &p)
             set_error("SPMV_FPGA_BLOCK must be a positive column count");
             return 1;
         }
-        p.fpga_width = (uint32_t)w;
+        p.csr.fpga_width = (uint32_t)w;
     }
     return 0;
 }
@@ -231,19 +231,19 @@ static int order_rows_by_block(spmv_plan &p, const IndexType *h_row_ptr, hipStre
     if (!p.nnz)
         return 0;
     std::vector<uint32_t> col(p.nnz);
-    SPMV_TRY(hipMemcpyAsync(col.data(), p.d_col, p.nnz * 4, hipMemcpyDeviceToHost, s));
+    SPMV_TRY(hipMemcpyAsync(col.data(), p.csr.col, p.nnz * 4, hipMemcpyDeviceToHost, s));
     SPMV_TRY(hipStreamSynchronize(s));
     bool sorted = true;
     for (IndexType r = 0; r < p.nr_rows && sorted; ++r)
         for (uint64_t k = uint64_t(h_row_ptr[r]) + 1; k < h_row_ptr[r + 1]; ++k)
-            if (col[k] / p.fpga_width < col[k - 1] / p.fpga_width) {
+            if (col[k] / p.csr.fpga_width < col[k - 1] / p.csr.fpga_width) {
                 sorted = false;
                 break;
             }
     if (sorted)
         return 0;
     std::vector<ValueType> val(p.nnz);
-    SPMV_TRY(hipMemcpyAsync(val.data(), p.d_val, p.nnz * sizeof(ValueType), hipMemcpyDeviceToHost, s));
+    SPMV_TRY(hipMemcpyAsync(val.data(), p.csr.val, p.nnz * sizeof(ValueType), hipMemcpyDeviceToHost, s));
     SPMV_TRY(hipStreamSynchronize(s));
     std::vector<uint32_t> idx;
     std::vector<uint32_t> c2(col);
@@ -254,14 +254,14 @@ static int order_rows_by_block(spmv_plan &p, const IndexType *h_row_ptr, hipStre
         for (uint64_t k = b; k < e; ++k)
             idx[k - b] = (uint32_t)k;
         std::stable_sort(idx.begin(), idx.end(),
-                         [&](uint32_t i, uint32_t j) { return col[i] / p.fpga_width < col[j] / p.fpga_width; });
+                         [&](uint32_t i, uint32_t j) { return col[i] / p.csr.fpga_width < col[j] / p.csr.fpga_width; });
         for (uint64_t k = b; k < e; ++k) {
             c2[k] = col[idx[k - b]];
             v2[k] = val[idx[k - b]];
         }
     }
-    SPMV_TRY(hipMemcpyAsync(p.d_col, c2.data(), p.nnz * 4, hipMemcpyHostToDevice, s));
-    SPMV_TRY(hipMemcpyAsync(p.d_val, v2.data(), p.nnz * sizeof(ValueType), hipMemcpyHostToDevice, s));
+    SPMV_TRY(hipMemcpyAsync(p.csr.col, c2.data(), p.nnz * 4, hipMemcpyHostToDevice, s));
+    SPMV_TRY(hipMemcpyAsync(p.csr.val, v2.data(), p.nnz * sizeof(ValueType), hipMemcpyHostToDevice, s));
     SPMV_TRY(hipStreamSynchronize(s));
     return 0;
 }
@@ -285,13 +285,13 @@ static layout_ops csr_row(const char *name, decltype(layout_ops::build) build)
         name, "build CSR layout", build, -1,
         nullptr, launch_of<launch_gold>, nullptr, warm_of<launch_gold>,
         csr_device_bytes,
-        [](const spmv_plan &p) -> uint64_t { return p.nlong; },   // units
+        [](const spmv_plan &p) -> uint64_t { return p.csr.nlong; },   // units
         [](const spmv_plan &) -> uint64_t { return kGoldLong; },  // unit_nnz
         one_block,
         [](const spmv_plan &) -> int { return 0; },            // format_bits
         [](const spmv_plan &p) -> uint64_t { return p.nnz; },  // stored_entries
-        [](const spmv_plan &p) -> void * { return p.d_col; },  // index_stream
-        -1, {0, 0}, set_tile_variant, false,  // tune_slot, product_variants, set_variant, host_y
+        [](const spmv_plan &p) -> void * { return p.csr.col.p; },  // index_stream
+        -1, {0, 0}, set_tile_variant, false, nullptr,  // tune_slot, product_variants, set_variant, host_y, flags_panels
     };
 }
 const layout_ops &gold_layout()

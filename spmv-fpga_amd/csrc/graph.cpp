@@ -96,19 +96,16 @@ int time_layout(spmv_plan &P, const ValueType *d_x, ValueType *d_y, hipStream_t 
 // workgroups fit beside the sweep's one 1024-thread workgroup per CU. Every step still computes
 // all of y = A x; the y of the last step is complete when the graph ends. Not for the tools
 // build's stealing variants (the combine re-arms their counters) or the fused combine.
-// (d_part: only a split sweep plan has partial sums.)
+// (sweep.part: only a split sweep plan has partial sums.)
 static bool graph_overlaps(const spmv_plan *p)
 {
-    return p->sweep_split > 1 && !p->d_panel_cnt && p->d_part && !(p->sweep_variant >= 37 && p->sweep_variant <= 39);
+    return p->sweep.split > 1 && !p->sweep.panel_cnt && p->sweep.part.p && !(p->sweep.variant >= 37 && p->sweep.variant <= 39);
 }
 
 static int graph_part2(spmv_plan *p)
 {
-    if (p->gpart.empty()) {
-        void *b = nullptr;
-        SPMV_TRY(hipMalloc(&b, p->nunits * (uint64_t(p->panel_rmax) + 1) * p->sweep_acc_bytes));
-        p->gpart.push_back(b);
-    }
+    if (!p->graph.part2.p)
+        SPMV_TRY(p->graph.part2.alloc_bytes(p->sweep.nunits * (uint64_t(p->panels.rmax) + 1) * p->sweep.acc_bytes));
     return 0;
 }
 
@@ -117,8 +114,8 @@ static int capture_overlapped(spmv_plan *p, const ValueType *d_x, ValueType *d_y
     constexpr int R = 2;  // partial buffers (longer rings measured slower)
     if (graph_part2(p))
         return 1;
-    if (!p->gstream2)
-        SPMV_TRY(hipStreamCreateWithFlags(&p->gstream2, hipStreamNonBlocking));
+    if (!p->graph.stream2)
+        SPMV_TRY(hipStreamCreateWithFlags(&p->graph.stream2, hipStreamNonBlocking));
     std::vector<hipEvent_t> ev(2 * size_t(iters), nullptr);
     auto destroy = [&] {
         for (hipEvent_t e : ev)
@@ -131,10 +128,10 @@ static int capture_overlapped(spmv_plan *p, const ValueType *d_x, ValueType *d_y
             set_error("spmv_plan_run_graph: hipEventCreate failed");
             return 1;
         }
-    hipStream_t a = p->gstream, b = p->gstream2;
+    hipStream_t a = p->graph.stream, b = p->graph.stream2;
     hipError_t e = hipStreamBeginCapture(a, hipStreamCaptureModeRelaxed);
     for (int k = 0; k < iters && e == hipSuccess; ++k) {
-        void *part = k % R ? p->gpart[k % R - 1] : p->d_part;
+        void *part = k % R ? p->graph.part2.p : p->sweep.part.p;
         if (k >= R)  // this buffer's previous combine is done
             e = hipStreamWaitEvent(a, ev[2 * (k - R) + 1], 0);
         if (e == hipSuccess)
@@ -153,7 +150,7 @@ static int capture_overlapped(spmv_plan *p, const ValueType *d_x, ValueType *d_y
     const std::string msg = "spmv_plan_run_graph: overlapped capture: ";
     if (e != hipSuccess)
         set_error(msg + hipGetErrorString(e));
-    const int rc = end_capture(a, e == hipSuccess, msg, &p->gexec);
+    const int rc = end_capture(a, e == hipSuccess, msg, &p->graph.exec);
     destroy();
     return rc;
 }
@@ -162,25 +159,25 @@ static int capture_overlapped(spmv_plan *p, const ValueType *d_x, ValueType *d_y
 // stream, one launch per step, and the combine of step k rides in step k + 1's sweep launch as
 // extra blocks that start on the CUs no unit holds and in the sweep's tail (sweep.hip,
 // combine_behind); a last k_sweep_combine finishes the last step. Partials alternate between
-// d_part and gpart[0]. No second stream, so no cross-queue hand-off between the steps.
+// sweep.part and graph.part2. No second stream, so no cross-queue hand-off between the steps.
 static int capture_behind(spmv_plan *p, const ValueType *d_x, ValueType *d_y, int iters)
 {
     if (graph_part2(p))
         return 1;
-    if (!p->d_gcount) {
-        SPMV_TRY(hipMalloc(&p->d_gcount, 2 * sizeof(uint32_t)));
-        SPMV_TRY(hipMemset(p->d_gcount, 0, 2 * sizeof(uint32_t)));
+    if (!p->graph.count) {
+        SPMV_TRY(p->graph.count.alloc(2));
+        SPMV_TRY(hipMemset(p->graph.count, 0, 2 * sizeof(uint32_t)));
     }
     int ncu = 0;
     SPMV_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device));
-    auto part_of = [&](int k) { return (k & 1) ? p->gpart[0] : p->d_part; };
-    hipStream_t a = p->gstream;
+    auto part_of = [&](int k) { return (k & 1) ? p->graph.part2.p : p->sweep.part.p; };
+    hipStream_t a = p->graph.stream;
     hipError_t e = hipStreamBeginCapture(a, hipStreamCaptureModeRelaxed);
     for (int k = 0; k < iters && e == hipSuccess; ++k) {
         sweep_behind bh;
         bh.cpart = k ? part_of(k - 1) : nullptr;
-        bh.ccount = p->d_gcount + (k & 1);
-        bh.cnext = p->d_gcount + ((k + 1) & 1);
+        bh.ccount = p->graph.count + (k & 1);
+        bh.cnext = p->graph.count + ((k + 1) & 1);
         bh.blocks = (uint32_t)std::max(ncu, 1);
         if (const char *v = ablation_env("SPMV_BEHIND_BLOCKS"))  // tools build: measured settings
             bh.blocks = (uint32_t)std::max(1, atoi(v));
@@ -193,7 +190,7 @@ static int capture_behind(spmv_plan *p, const ValueType *d_x, ValueType *d_y, in
     const std::string msg = "spmv_plan_run_graph: behind capture: ";
     if (e != hipSuccess)
         set_error(msg + hipGetErrorString(e));
-    return end_capture(a, e == hipSuccess, msg, &p->gexec);
+    return end_capture(a, e == hipSuccess, msg, &p->graph.exec);
 }
 
 // the capture form of a run_graph: 0 serial chain, 1 two-stream DAG, 2 behind. The tools build's
@@ -219,27 +216,24 @@ extern "C" int spmv_plan_run_graph(spmv_plan *p, const ValueType *d_x, ValueType
     }
     hipStream_t s = (hipStream_t)stream;
     SPMV_TRY(hipSetDevice(p->device));
-    if (!p->gexec || p->gx != d_x || p->gy != d_y || p->giters != iters) {
-        if (p->gexec) {
-            SPMV_TRY(hipGraphExecDestroy(p->gexec));
-            p->gexec = nullptr;
-        }
-        if (!p->gstream)
-            SPMV_TRY(hipStreamCreateWithFlags(&p->gstream, hipStreamNonBlocking));
+    if (!p->graph.exec || p->graph.x != d_x || p->graph.y != d_y || p->graph.iters != iters) {
+        SPMV_TRY(p->graph.drop_exec());
+        if (!p->graph.stream)
+            SPMV_TRY(hipStreamCreateWithFlags(&p->graph.stream, hipStreamNonBlocking));
         const int form = iters >= 2 ? graph_form(p) : 0;
         if (form == 2   ? capture_behind(p, d_x, d_y, iters)
             : form == 1 ? capture_overlapped(p, d_x, d_y, iters)
-                        : capture_serial(p, d_x, d_y, iters, p->gstream, &p->gexec))
+                        : capture_serial(p, d_x, d_y, iters, p->graph.stream, &p->graph.exec))
             return 1;
-        p->gx = d_x;
-        p->gy = d_y;
-        p->giters = iters;
+        p->graph.x = d_x;
+        p->graph.y = d_y;
+        p->graph.iters = iters;
     }
     hipEvent_t e1 = nullptr;
-    if (p->timing && timing_begin(p, s, &e1))
+    if (p->timing.on && timing_begin(p, s, &e1))
         return 1;
-    SPMV_TRY(hipGraphLaunch(p->gexec, s));
-    if (p->timing)
+    SPMV_TRY(hipGraphLaunch(p->graph.exec, s));
+    if (p->timing.on)
         SPMV_TRY(hipEventRecord(e1, s));
     return 0;
 }

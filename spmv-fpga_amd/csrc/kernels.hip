@@ -264,17 +264,18 @@ __global__ void k_pack(const IndexType *__restrict__ col_src, const V *__restric
 
 hipError_t launch_spmv(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm)
 {
-    if (p.ntiles == 0)
+    const tiles_state &w = p.tiles;
+    if (w.ntiles == 0)
         return hipSuccess;
     const uint64_t waves_per_block = kBlockThreads / kWave;
-    const uint64_t nblk = (p.ntiles + waves_per_block - 1) / waves_per_block;
-    const uint32_t xcd_chunk = p.tile_xcd ? (uint32_t)((nblk + 7) / 8) : 0u;
+    const uint64_t nblk = (w.ntiles + waves_per_block - 1) / waves_per_block;
+    const uint32_t xcd_chunk = w.xcd ? (uint32_t)((nblk + 7) / 8) : 0u;
     const uint64_t blocks = xcd_chunk ? 8ull * xcd_chunk : nblk;
 #define SPMV_LAUNCH(VAR, CB)                                                                      \
     launch_or_warm(warm, k_spmv_tiles<ValueType, kTileSteps, VAR, CB>, dim3((unsigned)blocks),       \
-                       dim3(kBlockThreads), 0, s, p.d_col, p.d_colnar, p.d_tile_cbase, p.d_val,     \
-                       p.d_rowend, p.d_tile_info, p.d_row_id, d_x, d_y, p.d_head, p.d_tail, p.nnz, \
-                       p.ntiles, xcd_chunk)
+                       dim3(kBlockThreads), 0, s, w.col.get(), w.colnar.p, w.cbase.get(), w.val.get(), \
+                       w.rowend.get(), w.tile_info.get(), w.row_id.get(), d_x, d_y, w.head.get(), w.tail.get(),  \
+                       p.nnz, w.ntiles, xcd_chunk)
 #define SPMV_VARIANTS(CB)                    \
     switch (p.variant & 3) {                 \
     case 0: SPMV_LAUNCH(0, CB); break;       \
@@ -282,11 +283,11 @@ hipError_t launch_spmv(const spmv_plan &p, const ValueType *d_x, ValueType *d_y,
     case 2: SPMV_LAUNCH(2, CB); break;       \
     default: SPMV_LAUNCH(3, CB); break;      \
     }
-    if (p.tile_col_bytes == 1) {
+    if (w.col_bytes == 1) {
         SPMV_VARIANTS(1)
-    } else if (p.tile_col_bytes == 2 && p.tile_clustered) {
+    } else if (w.col_bytes == 2 && w.clustered) {
         SPMV_VARIANTS(3)
-    } else if (p.tile_col_bytes == 2) {
+    } else if (w.col_bytes == 2) {
         SPMV_VARIANTS(2)
     } else {
         SPMV_VARIANTS(4)
@@ -298,11 +299,12 @@ hipError_t launch_spmv(const spmv_plan &p, const ValueType *d_x, ValueType *d_y,
 
 hipError_t launch_fixup(const spmv_plan &p, ValueType *d_y, hipStream_t s, bool warm)
 {
-    if (p.ncross == 0)
+    const tiles_state &w = p.tiles;
+    if (w.ncross == 0)
         return hipSuccess;
-    const uint64_t blocks = (p.ncross + 255) / 256;
-    launch_or_warm(warm, k_fixup<ValueType>, dim3((unsigned)blocks), dim3(256), 0, s, p.d_cross, p.ncross,
-                       p.d_head, p.d_tail, p.d_row_id, d_y);
+    const uint64_t blocks = (w.ncross + 255) / 256;
+    launch_or_warm(warm, k_fixup<ValueType>, dim3((unsigned)blocks), dim3(256), 0, s, w.cross.get(), w.ncross,
+                   w.head.get(), w.tail.get(), w.row_id.get(), d_y);
     return hipGetLastError();
 }
 

@@ -147,7 +147,7 @@ static int multi_create(spmv_multi **out, int device, int op, const csr_slice &s
         set_error("spmv_multi: internal: the native path needs a slice plan");
         return 1;
     }
-    native = native || m->plan->sweep_nvec > 1;  // the automatic choice took the sweep
+    native = native || m->plan->sweep.nvec > 1;  // the automatic choice took the sweep
     m->native = native;
     if (native) {
         // load the code object (a sweep plan's build has warmed launch_sweep_multi)

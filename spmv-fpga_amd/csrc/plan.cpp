@@ -209,7 +209,7 @@ int plan_create_from_slice(spmv_plan **out, int device, int op, const csr_slice 
                 continue;
             std::unique_ptr<spmv_plan> q = fresh();
             if (k == kKernelSlices)
-                q->slice_pad_limit = 2.0;  // a slice layout padded beyond 2x is built as tiles instead
+                q->slices.pad_limit = 2.0;  // a slice layout padded beyond 2x is built as tiles instead
             double t = 1e30;
             if (build_layout(*q, k, true, h_row_ptr, d_col, d_val, s) ||
                 time_layout(*q, (const ValueType *)tx.p, (ValueType *)ty.p, s, &t)) {
@@ -243,14 +243,14 @@ int plan_create_from_slice(spmv_plan **out, int device, int op, const csr_slice 
         // keep the tiles, which gather a band's x from fewer lines per instruction (the fp32
         // band is 13 % faster in slices)
         std::unique_ptr<spmv_plan> r = fresh();
-        r->slice_pad_limit = 1.15;
+        r->slices.pad_limit = 1.15;
         const int rc = build_layout(*r, kKernelSlices, true, h_row_ptr, d_col, d_val, s);
         if (rc == 0 && r->kernel == kKernelSlices &&
-            (r->slice_off_bytes == 2 || (r->slice_off_bytes == 1 && sizeof(ValueType) == 4)) &&
-            double(r->slice_slots) * kWave <= 1.15 * double(nnz)) {
+            (r->slices.off_bytes == 2 || (r->slices.off_bytes == 1 && sizeof(ValueType) == 4)) &&
+            double(r->slices.slots) * kWave <= 1.15 * double(nnz)) {
             p.swap(r);
         } else if (rc == 0 && r->kernel == kKernelTiles) {  // padding too high: built as tiles
-            r->slice_pad_limit = 0.0;
+            r->slices.pad_limit = 0.0;
             p.swap(r);
         } else {
             r.reset();
@@ -268,7 +268,7 @@ int plan_create_from_slice(spmv_plan **out, int device, int op, const csr_slice 
             const uint64_t wgs = (uint64_t)device_cu_count(device) * (1024 / p->sweep_threads);
             if (min_panels(nr_rows, sweep_rmax(p->sweep_threads, 8, multi_nvec)) >= wgs) {
                 std::unique_ptr<spmv_plan> r = fresh();
-                r->sweep_nvec = multi_nvec;
+                r->sweep.nvec = multi_nvec;
                 if (build_layout(*r, kKernelSweep, false, h_row_ptr, d_col, d_val, s) == 0) {
                     trace("build multi-vector sweep layout", s);
                     *out = r.release();
@@ -283,13 +283,13 @@ int plan_create_from_slice(spmv_plan **out, int device, int op, const csr_slice 
             }
         }
         if (kernel == kKernelBinned && requested < 0) {
-            p->bin_skew_limit = 2.0;  // automatic: skewed matrices stay on the sweep
+            p->binned.skew_limit = 2.0;  // automatic: skewed matrices stay on the sweep
             // and so do matrices with a row above 0.3x a panel's mean entries: 2M x 6M fp32 with
             // 64 rows of L (profiles/r03e_skew_rowlimit.jsonl; L / mean 0.12, 0.24, 0.44, 0.81):
             // binned 0.136 / 0.178 / 0.254 / 0.282 ms, sweep 0.155 / 0.183 / 0.225 / 0.298
-            p->bin_row_limit = 0.3;
+            p->binned.row_limit = 0.3;
             if (const char *e = std::getenv("SPMV_BIN_ROW_LIMIT"))
-                p->bin_row_limit = std::atof(e);
+                p->binned.row_limit = std::atof(e);
         }
         if (build_layout(*p, kernel, requested < 0, h_row_ptr, d_col, d_val, s))
             return 1;
@@ -301,14 +301,14 @@ int plan_create_from_slice(spmv_plan **out, int device, int op, const csr_slice 
 
 int timing_begin(spmv_plan *p, hipStream_t s, hipEvent_t *e1)
 {
-    while (p->ev_used + 2 > p->ev.size()) {
+    while (p->timing.used + 2 > p->timing.ev.size()) {
         hipEvent_t e;
         SPMV_TRY(hipEventCreate(&e));
-        p->ev.push_back(e);
+        p->timing.ev.push_back(e);
     }
-    const hipEvent_t e0 = p->ev[p->ev_used];
-    *e1 = p->ev[p->ev_used + 1];
-    p->ev_used += 2;
+    const hipEvent_t e0 = p->timing.ev[p->timing.used];
+    *e1 = p->timing.ev[p->timing.used + 1];
+    p->timing.used += 2;
     SPMV_TRY(hipEventRecord(e0, s));
     return 0;
 }
@@ -334,31 +334,6 @@ int run_impl(spmv_plan *p, const ValueType *d_x, ValueType *d_y, hipStream_t s, 
 }  // namespace spmvhw
 
 using namespace spmvhw;
-
-spmv_plan::~spmv_plan()
-{
-    (void)hipSetDevice(device);
-    (void)hipDeviceSynchronize();
-    for (void *ptr : {(void *)d_col, (void *)d_val, (void *)d_rowend, (void *)d_tile_info,
-                      (void *)d_row_id, (void *)d_head, (void *)d_tail, (void *)d_cross, (void *)d_s_col,
-                      (void *)d_s_row, (void *)d_s_val, (void *)d_panel_row, (void *)d_unit_ent, (void *)d_part, (void *)d_gcount, (void *)d_steal, (void *)d_panel_cnt, (void *)d_unit_panel, (void *)d_panel_unit, (void *)d_rp,
-                      (void *)d_s_cbase, (void *)d_s_row16, (void *)d_s_d8, (void *)d_s_dbase, (void *)d_s_side, d_colnar, (void *)d_tile_cbase, (void *)d_kptr, (void *)d_kpos,
-                      (void *)d_rp2, (void *)d_rl, (void *)d_chunk_row, (void *)d_bpart, (void *)d_slot_off,
-                      (void *)d_sbase, (void *)d_slice_len, (void *)d_b_val, (void *)d_b_colw, (void *)d_b_rowp,
-                      d_b_prod_alloc, (void *)d_b_seg, (void *)d_b_seg_hi, (void *)d_b_ub, (void *)d_b_uwin})
-        if (ptr)
-            (void)hipFree(ptr);
-    for (void *ptr : gpart)
-        (void)hipFree(ptr);
-    for (hipEvent_t e : ev)
-        (void)hipEventDestroy(e);
-    if (gexec)
-        (void)hipGraphExecDestroy(gexec);
-    if (gstream)
-        (void)hipStreamDestroy(gstream);
-    if (gstream2)
-        (void)hipStreamDestroy(gstream2);
-}
 
 uint64_t spmv_plan::device_bytes() const { return layout_of(kernel).device_bytes(*this); }
 
@@ -444,7 +419,7 @@ int spmv_plan_run(const spmv_plan *cp, const ValueType *d_x, ValueType *d_y, voi
     }
     spmv_plan *p = const_cast<spmv_plan *>(cp);
     SPMV_TRY(hipSetDevice(p->device));
-    return run_impl(p, d_x, d_y, (hipStream_t)stream, p->timing);
+    return run_impl(p, d_x, d_y, (hipStream_t)stream, p->timing.on);
 }
 
 int spmv_plan_get_stats(const spmv_plan *p, spmv_plan_stats *st)
@@ -497,10 +472,9 @@ int spmv_plan_set_variant(spmv_plan *p, int variant)
     if (L.set_variant(*p, variant))
         return 1;
     // a graph captured with the previous variant must not be replayed
-    if (p->gexec) {
+    if (p->graph.exec) {
         (void)hipSetDevice(p->device);
-        (void)hipGraphExecDestroy(p->gexec);
-        p->gexec = nullptr;
+        (void)p->graph.drop_exec();
     }
     return 0;
 }
@@ -511,8 +485,8 @@ int spmv_plan_set_timing(spmv_plan *p, int enable)
         set_error("spmv_plan_set_timing: null plan");
         return 1;
     }
-    p->timing = enable != 0;
-    p->ev_used = 0;
+    p->timing.on = enable != 0;
+    p->timing.used = 0;
     return 0;
 }
 
@@ -525,14 +499,14 @@ int spmv_plan_get_timing(spmv_plan *p, double *mean_ms, double *total_ms, int *l
     SPMV_TRY(hipSetDevice(p->device));
     double tot = 0.0;
     int n = 0;
-    for (size_t i = 0; i + 1 < p->ev_used; i += 2) {
-        SPMV_TRY(hipEventSynchronize(p->ev[i + 1]));
+    for (size_t i = 0; i + 1 < p->timing.used; i += 2) {
+        SPMV_TRY(hipEventSynchronize(p->timing.ev[i + 1]));
         float ms = 0.f;
-        SPMV_TRY(hipEventElapsedTime(&ms, p->ev[i], p->ev[i + 1]));
+        SPMV_TRY(hipEventElapsedTime(&ms, p->timing.ev[i], p->timing.ev[i + 1]));
         tot += ms;
         ++n;
     }
-    p->ev_used = 0;
+    p->timing.used = 0;
     if (mean_ms)
         *mean_ms = n ? tot / n : 0.0;
     if (total_ms)

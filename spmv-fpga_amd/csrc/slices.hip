@@ -325,12 +325,13 @@ template <typename A>
 static void launch_slices_multi_acc(const spmv_plan &p, int nvec, const ValueType *d_X, ValueType *d_Y, hipStream_t s,
                                     bool warm)
 {
-    const uint32_t nsl = (uint32_t)p.nslices;
+    const slices_state &w = p.slices;
+    const uint32_t nsl = (uint32_t)w.nslices;
     const dim3 grid((nsl + kSliceThreads / kWave - 1) / (kSliceThreads / kWave));
 #define SLM(OB, K)                                                                                               \
     launch_or_warm(warm, k_spmv_slices_multi<ValueType, OB, K, multi_pairs(K), A>, grid, dim3(kSliceThreads), 0, \
-                   s, (const ValueType *)p.d_val, (const void *)p.d_colnar, (const uint32_t *)p.d_sbase,         \
-                   (const uint32_t *)p.d_slot_off, (const uint32_t *)p.d_slice_len, d_X, d_Y, p.nr_rows, nsl)
+                   s, (const ValueType *)w.val.get(), (const void *)w.off.p, (const uint32_t *)w.sbase.get(),    \
+                   (const uint32_t *)w.slot_off.get(), (const uint32_t *)w.len.get(), d_X, d_Y, p.nr_rows, nsl)
 #define SLK(OB)                                                                                                  \
     do {                                                                                                         \
         if (nvec == 2)                                                                                           \
@@ -340,11 +341,11 @@ static void launch_slices_multi_acc(const spmv_plan &p, int nvec, const ValueTyp
         else                                                                                                     \
             SLM(OB, 8);                                                                                          \
     } while (0)
-    if (p.slice_off_bytes == 1)
+    if (w.off_bytes == 1)
         SLK(1);
-    else if (p.slice_off_bytes == 2 && p.slice_clustered)
+    else if (w.off_bytes == 2 && w.clustered)
         SLK(3);
-    else if (p.slice_off_bytes == 2)
+    else if (w.off_bytes == 2)
         SLK(2);
     else
         SLK(4);
@@ -362,7 +363,7 @@ hipError_t launch_slices_multi(const spmv_plan &p, int nvec, const ValueType *d_
     if (p.nr_rows == 0)
         return hipSuccess;
     if constexpr (sizeof(ValueType) == 4) {
-        if (p.slice_acc_native) {  // fp32 accumulator (env SPMV_SLICE_ACC=32)
+        if (p.slices.acc_native) {  // fp32 accumulator (env SPMV_SLICE_ACC=32)
             launch_slices_multi_acc<ValueType>(p, nvec, d_X, d_Y, s, warm);
             return hipGetLastError();
         }
@@ -375,12 +376,13 @@ hipError_t launch_slices(const spmv_plan &p, const ValueType *d_x, ValueType *d_
 {
     if (p.nr_rows == 0)
         return hipSuccess;
-    const uint32_t nsl = (uint32_t)p.nslices;
+    const slices_state &w = p.slices;
+    const uint32_t nsl = (uint32_t)w.nslices;
     const dim3 grid((nsl + kSliceThreads / kWave - 1) / (kSliceThreads / kWave));
 #define SLV(OB, PU, TAIL)                                                                                        \
     launch_or_warm(warm, k_spmv_slices<ValueType, OB, PU, TAIL>, grid, dim3(kSliceThreads), 0, s,                 \
-                   (const ValueType *)p.d_val, (const void *)p.d_colnar, (const uint32_t *)p.d_sbase,             \
-                   (const uint32_t *)p.d_slot_off, (const uint32_t *)p.d_slice_len, d_x, d_y, p.nr_rows, nsl)
+                   (const ValueType *)w.val.get(), (const void *)w.off.p, (const uint32_t *)w.sbase.get(),       \
+                   (const uint32_t *)w.slot_off.get(), (const uint32_t *)w.len.get(), d_x, d_y, p.nr_rows, nsl)
     // variant (spmv_plan_set_variant): 0 = 4 pairs per iteration, pairs past the slice's end
     // skipped (default: 27-point 0.450 vs 0.508 ms, 7-point 0.126 vs 0.131 when they re-read the
     // first pair); 1 = 2 pairs, 2 = 7 pairs, 3 = 4 pairs re-reading
@@ -396,16 +398,16 @@ hipError_t launch_slices(const spmv_plan &p, const ValueType *d_x, ValueType *d_
             SLV(OB, 4, true);                                                                                    \
     } while (0)
     if constexpr (sizeof(ValueType) == 4) {
-        if (p.slice_acc_native) {  // fp32 accumulator (default variant only)
+        if (p.slices.acc_native) {  // fp32 accumulator (default variant only)
 #define SLF(OB)                                                                                                  \
     launch_or_warm(warm, k_spmv_slices<ValueType, OB, 4, true, ValueType>, grid, dim3(kSliceThreads), 0, s,       \
-                   (const ValueType *)p.d_val, (const void *)p.d_colnar, (const uint32_t *)p.d_sbase,             \
-                   (const uint32_t *)p.d_slot_off, (const uint32_t *)p.d_slice_len, d_x, d_y, p.nr_rows, nsl)
-            if (p.slice_off_bytes == 1)
+                   (const ValueType *)w.val.get(), (const void *)w.off.p, (const uint32_t *)w.sbase.get(),       \
+                   (const uint32_t *)w.slot_off.get(), (const uint32_t *)w.len.get(), d_x, d_y, p.nr_rows, nsl)
+            if (w.off_bytes == 1)
                 SLF(1);
-            else if (p.slice_off_bytes == 2 && p.slice_clustered)
+            else if (w.off_bytes == 2 && w.clustered)
                 SLF(3);
-            else if (p.slice_off_bytes == 2)
+            else if (w.off_bytes == 2)
                 SLF(2);
             else
                 SLF(4);
@@ -413,11 +415,11 @@ hipError_t launch_slices(const spmv_plan &p, const ValueType *d_x, ValueType *d_
             return hipGetLastError();
         }
     }
-    if (p.slice_off_bytes == 1)
+    if (w.off_bytes == 1)
         SL(1);
-    else if (p.slice_off_bytes == 2 && p.slice_clustered)
+    else if (w.off_bytes == 2 && w.clustered)
         SL(3);
-    else if (p.slice_off_bytes == 2)
+    else if (w.off_bytes == 2)
         SL(2);
     else
         SL(4);
@@ -598,38 +600,39 @@ int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
         }
     }
     so[S] = (uint32_t)slots;
-    if (p.slice_pad_limit > 0.0 && double(slots) * kWave > p.slice_pad_limit * double(p.nnz)) {
+    if (p.slices.pad_limit > 0.0 && double(slots) * kWave > p.slices.pad_limit * double(p.nnz)) {
         set_error("slices: padding above the automatic choice's limit");
         return 2;  // decided from row_ptr alone, before any allocation
     }
-    p.nslices = S;
-    p.slice_slots = slots;
+    slices_state &w = p.slices;
+    w.nslices = S;
+    w.slots = slots;
     const uint64_t E = slots * kWave;
     device_scratch tcol, tspan, trp;
-    SPMV_TRY(hipMalloc((void **)&p.d_slot_off, (S + 1) * 4));
-    SPMV_TRY(hipMalloc((void **)&p.d_slice_len, std::max<size_t>(n, 1) * 4));
-    SPMV_TRY(hipMalloc((void **)&p.d_val, std::max<uint64_t>(E, 2) * sizeof(ValueType)));
-    SPMV_TRY(hipMalloc((void **)&p.d_sbase, std::max<uint64_t>(slots, 1) * 4));
+    SPMV_TRY(w.slot_off.alloc(S + 1));
+    SPMV_TRY(w.len.alloc(std::max<size_t>(n, 1)));
+    SPMV_TRY(w.val.alloc(std::max<uint64_t>(E, 2)));
+    SPMV_TRY(w.sbase.alloc(std::max<uint64_t>(slots, 1)));
     SPMV_TRY(hipMalloc(&tcol.p, std::max<uint64_t>(E, 2) * 4));
     SPMV_TRY(hipMalloc(&tspan.p, 4));
     SPMV_TRY(hipMalloc(&trp.p, (size_t(n) + 1) * 4));
-    SPMV_TRY(hipMemcpyAsync(p.d_slot_off, so.data(), (S + 1) * 4, hipMemcpyHostToDevice, s));
+    SPMV_TRY(hipMemcpyAsync(w.slot_off.get(), so.data(), (S + 1) * 4, hipMemcpyHostToDevice, s));
     if (n)
-        SPMV_TRY(hipMemcpyAsync(p.d_slice_len, len.data(), size_t(n) * 4, hipMemcpyHostToDevice, s));
+        SPMV_TRY(hipMemcpyAsync(w.len.get(), len.data(), size_t(n) * 4, hipMemcpyHostToDevice, s));
     SPMV_TRY(hipMemcpyAsync(trp.p, h_rp, (size_t(n) + 1) * 4, hipMemcpyHostToDevice, s));
     SPMV_TRY(hipMemsetAsync(tspan.p, 0, 4, s));
     uint32_t span = 0;
     if (n) {
         hipLaunchKernelGGL(k_slices_fill, dim3((n + 255) / 256), dim3(256), 0, s, (const IndexType *)trp.p, d_col_src,
-                           d_val_src, n, p.d_slot_off, p.d_val, (uint32_t *)tcol.p);
+                           d_val_src, n, w.slot_off.get(), w.val.get(), (uint32_t *)tcol.p);
         SPMV_TRY(hipGetLastError());
         const uint32_t rest = (uint32_t)(S * kWave - n);
         if (rest)
-            hipLaunchKernelGGL(k_slices_tail, dim3((rest + 63) / 64), dim3(64), 0, s, n, (uint32_t)S, p.d_slot_off,
-                               p.d_val, (uint32_t *)tcol.p);
+            hipLaunchKernelGGL(k_slices_tail, dim3((rest + 63) / 64), dim3(64), 0, s, n, (uint32_t)S, w.slot_off.get(),
+                               w.val.get(), (uint32_t *)tcol.p);
         SPMV_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_slices_base, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off, (uint32_t)S,
-                           (const uint32_t *)tcol.p, p.d_sbase, (uint32_t *)tspan.p);
+        hipLaunchKernelGGL(k_slices_base, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, w.slot_off.get(), (uint32_t)S,
+                           (const uint32_t *)tcol.p, w.sbase.get(), (uint32_t *)tspan.p);
         SPMV_TRY(hipGetLastError());
         SPMV_TRY(hipMemcpyAsync(&span, tspan.p, 4, hipMemcpyDeviceToHost, s));
         SPMV_TRY(hipStreamSynchronize(s));
@@ -637,58 +640,58 @@ int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
     // env SPMV_SLICE_ACC=32 (fp32 library): fp32 row accumulator, bitwise spmv_gold in fp32
     {
         const char *aenv = std::getenv("SPMV_SLICE_ACC");
-        p.slice_acc_native = sizeof(ValueType) == 4 && aenv && std::atoi(aenv) == 32;
+        w.acc_native = sizeof(ValueType) == 4 && aenv && std::atoi(aenv) == 32;
     }
     // env SPMV_SLICE_NARROW=0 keeps 32-bit columns
     const char *nenv = ablation_env("SPMV_SLICE_NARROW");
     const bool narrow = !(nenv && nenv[0] == '0');
     int ob = !narrow ? 4 : span < 256u ? 1 : span < 65536u ? 2 : 4;
     if (ob == 4 && narrow && n) {  // try up to 4 clusters of 16384 columns per slot
-        uint32_t *sb4 = nullptr, bad = 1;
-        SPMV_TRY(hipMalloc((void **)&sb4, std::max<uint64_t>(slots, 1) * 16));
+        device_buf<uint32_t> sb4;
+        uint32_t bad = 1;
+        SPMV_TRY(sb4.alloc(std::max<uint64_t>(slots, 1) * 4));
         SPMV_TRY(hipMemsetAsync(tspan.p, 0, 4, s));
-        hipLaunchKernelGGL(k_slices_clusters, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off,
-                           (uint32_t)S, (const uint32_t *)tcol.p, sb4, (uint32_t *)tspan.p);
+        hipLaunchKernelGGL(k_slices_clusters, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, w.slot_off.get(),
+                           (uint32_t)S, (const uint32_t *)tcol.p, sb4.get(), (uint32_t *)tspan.p);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess)
             e = hipMemcpyAsync(&bad, tspan.p, 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess)
             e = hipStreamSynchronize(s);
         if (e != hipSuccess || bad) {
-            (void)hipFree(sb4);
+            (void)sb4.release();
             SPMV_TRY(e);
         } else {
-            SPMV_TRY(hipFree(p.d_sbase));
-            p.d_sbase = sb4;
-            SPMV_TRY(hipMalloc(&p.d_colnar, std::max<uint64_t>(E, 2) * 2));
-            hipLaunchKernelGGL(k_slices_off_cl, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off,
-                               (uint32_t)S, (const uint32_t *)tcol.p, (const uint32_t *)p.d_sbase,
-                               (uint16_t *)p.d_colnar);
+            w.sbase.swap(sb4);  // the plan takes the cluster bases; the slot bases are freed
+            SPMV_TRY(sb4.release());
+            SPMV_TRY(w.off.alloc_bytes(std::max<uint64_t>(E, 2) * 2));
+            hipLaunchKernelGGL(k_slices_off_cl, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, w.slot_off.get(),
+                               (uint32_t)S, (const uint32_t *)tcol.p, w.sbase.get(),
+                               (uint16_t *)w.off.p);
             SPMV_TRY(hipGetLastError());
             SPMV_TRY(hipStreamSynchronize(s));
-            p.slice_off_bytes = 2;
-            p.slice_clustered = true;
+            w.off_bytes = 2;
+            w.clustered = true;
             return 0;
         }
     }
-    p.slice_off_bytes = ob;
+    w.off_bytes = ob;
     if (ob == 4) {  // absolute columns: padding lanes get column 0 (masked), bases 0
         if (E) {
             hipLaunchKernelGGL(k_slices_abs, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, (uint32_t *)tcol.p, E);
             SPMV_TRY(hipGetLastError());
         }
-        SPMV_TRY(hipMemsetAsync(p.d_sbase, 0, std::max<uint64_t>(slots, 1) * 4, s));
-        p.d_colnar = tcol.p;
-        tcol.p = nullptr;
+        SPMV_TRY(hipMemsetAsync(w.sbase.get(), 0, std::max<uint64_t>(slots, 1) * 4, s));
+        w.off.swap(tcol);  // the plan takes the column array
     } else {
-        SPMV_TRY(hipMalloc(&p.d_colnar, std::max<uint64_t>(E, 2) * ob));
+        SPMV_TRY(w.off.alloc_bytes(std::max<uint64_t>(E, 2) * ob));
         if (n) {
             if (ob == 1)
-                hipLaunchKernelGGL(k_slices_off<uint8_t>, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off,
-                                   (uint32_t)S, (const uint32_t *)tcol.p, p.d_sbase, (uint8_t *)p.d_colnar);
+                hipLaunchKernelGGL(k_slices_off<uint8_t>, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, w.slot_off.get(),
+                                   (uint32_t)S, (const uint32_t *)tcol.p, w.sbase.get(), (uint8_t *)w.off.p);
             else
-                hipLaunchKernelGGL(k_slices_off<uint16_t>, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, p.d_slot_off,
-                                   (uint32_t)S, (const uint32_t *)tcol.p, p.d_sbase, (uint16_t *)p.d_colnar);
+                hipLaunchKernelGGL(k_slices_off<uint16_t>, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, s, w.slot_off.get(),
+                                   (uint32_t)S, (const uint32_t *)tcol.p, w.sbase.get(), (uint16_t *)w.off.p);
             SPMV_TRY(hipGetLastError());
         }
     }
@@ -699,14 +702,14 @@ int build_slices(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
 // ---- the slices' row of the layout table (spmv_internal.hpp layout_ops) ----
 static uint64_t slices_device_bytes(const spmv_plan &p)  // padded entries, slot bases, slice offsets, row lengths
 {
-    return p.slice_slots * kWave * (sizeof(ValueType) + p.slice_off_bytes) + p.slice_slots * (p.slice_clustered ? 16 : 4) +
-           (p.nslices + 1) * 4 +
+    return p.slices.slots * kWave * (sizeof(ValueType) + p.slices.off_bytes) + p.slices.slots * (p.slices.clustered ? 16 : 4) +
+           (p.slices.nslices + 1) * 4 +
            uint64_t(p.nr_rows) * 4;
 }
 
 static int slices_format_bits(const spmv_plan &p)
 {
-    return (p.slice_off_bytes < 4 ? 1 : 0) | (p.slice_off_bytes == 1 ? 8 : 0) | (p.slice_clustered ? 16 : 0);
+    return (p.slices.off_bytes < 4 ? 1 : 0) | (p.slices.off_bytes == 1 ? 8 : 0) | (p.slices.clustered ? 16 : 0);
 }
 
 const layout_ops &slices_layout()
@@ -715,13 +718,13 @@ const layout_ops &slices_layout()
         "slices", "build slice layout", build_slices, kKernelTiles,  // (> 2^32 stored entries, or the padding limit)
         nullptr, launch_of<launch_slices>, nullptr, warm_of<launch_slices>,
         slices_device_bytes,
-        [](const spmv_plan &p) -> uint64_t { return p.nslices; },              // units
-        [](const spmv_plan &p) -> uint64_t { return p.slice_slots * kWave; },  // unit_nnz: stored entries with padding
+        [](const spmv_plan &p) -> uint64_t { return p.slices.nslices; },              // units
+        [](const spmv_plan &p) -> uint64_t { return p.slices.slots * kWave; },  // unit_nnz: stored entries with padding
         one_block,
         slices_format_bits,
-        [](const spmv_plan &p) -> uint64_t { return p.slice_slots * kWave; },  // stored_entries
-        [](const spmv_plan &p) -> void * { return p.d_colnar; },               // index_stream
-        2, {0, 0}, set_tile_variant, false,  // tune_slot, product_variants, set_variant, host_y
+        [](const spmv_plan &p) -> uint64_t { return p.slices.slots * kWave; },  // stored_entries
+        [](const spmv_plan &p) -> void * { return p.slices.off.p; },             // index_stream
+        2, {0, 0}, set_tile_variant, false, nullptr,  // tune_slot, product_variants, set_variant, host_y, flags_panels
     };
     return row;
 }

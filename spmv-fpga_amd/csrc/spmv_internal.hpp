@@ -25,6 +25,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "csr_hw_wrapper.h"
@@ -66,6 +67,236 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v0)
     return v;
 }
 
+// Device memory with one owner, freed when the owner goes: a build step's scratch on scope exit,
+// a plan's buffers with the plan. Not copyable, so a buffer handed to a kernel launch by mistake
+// does not compile: a kernel argument is get() (or p), never the buffer.
+struct device_scratch {
+    void *p = nullptr;
+    device_scratch() = default;
+    device_scratch(const device_scratch &) = delete;
+    device_scratch &operator=(const device_scratch &) = delete;
+    // `bytes` of device memory; what the buffer held before is freed first
+    hipError_t alloc_bytes(uint64_t bytes)
+    {
+        const hipError_t e = release();
+        return e != hipSuccess ? e : hipMalloc(&p, bytes);
+    }
+    // frees early (where that bounds a build's peak memory, or before a rebuild). swap() trades the
+    // memory with another buffer: a build hands the plan a finished array, and its scratch frees
+    // what the plan held
+    hipError_t release()
+    {
+        void *q = p;
+        p = nullptr;
+        return q ? hipFree(q) : hipSuccess;
+    }
+    void swap(device_scratch &other) { std::swap(p, other.p); }
+    ~device_scratch() { (void)release(); }
+};
+// ... of `count` elements of T
+template <typename T>
+struct device_buf : device_scratch {
+    T *get() const { return static_cast<T *>(p); }
+    operator T *() const { return get(); }
+    hipError_t alloc(uint64_t count) { return alloc_bytes(count * sizeof(T)); }
+    void swap(device_buf &other) { device_scratch::swap(other); }  // (only with its own type)
+};
+
+// ---- a plan's state, one struct per layout (DESIGN.md §3 "The layout table") ----
+// A layout's file reads `panels`, `release` and its own struct; every device buffer a plan owns is
+// a device_buf / device_scratch member, and a raw pointer member is borrowed (its comment says
+// from whom).
+
+// flagged tiles (kernel 0; tiles.cpp, kernels.hip): the representation in this file's head comment
+struct tiles_state {
+    uint64_t nnz_pad = 0, ntiles = 0;
+    device_buf<uint32_t> col;
+    device_scratch colnar;           // narrow form: u16 or u8 offsets from cbase (col freed)
+    device_buf<uint32_t> cbase;
+    int col_bytes = 4;               // 4 (col), 2 or 1 (colnar)
+    bool clustered = false;          // 2-byte columns as (cluster << 14) | offset, 4 bases per tile
+    bool xcd = false;                // XCD-contiguous tile order (env SPMV_TILE_XCD=1); measured
+                                     // slower on stencils (+6 %), 2 % faster on banded
+    device_buf<ValueType> val;
+    device_buf<uint32_t> rowend, tile_info, row_id;
+    device_buf<ValueType> head, tail;
+    device_buf<uint32_t> cross;      // rows crossing tile boundaries: (row, first tile, last tile)
+    uint64_t ncross = 0;
+};
+
+// gold order and the reference FPGA path's order (kernels 1 and 3, gold.hip): plain CSR
+struct csr_state {
+    device_buf<uint32_t> rp;          // rebased row_ptr[nr_rows + 1]
+    device_buf<uint32_t> col;
+    device_buf<ValueType> val;
+    uint64_t nlong = 0;               // rows with more than kGoldLong entries (stats)
+    int fpga_vf = 1;                  // kernel 3: vectorisation factor (env SPMV_FPGA_VF)
+    uint32_t fpga_width = 32768;      // kernel 3: column-block width (env SPMV_FPGA_BLOCK)
+                                      // (kernel 4 takes the same two: fpga_params)
+};
+
+// blocked (kernel 4, blocked.hip): entries by (block, row)
+struct blocked_state {
+    device_buf<ValueType> val;
+    device_buf<uint16_t> col;         // block-relative columns
+    uint64_t nunits = 0;              // workgroups of the main kernel
+    device_buf<uint32_t> unit_block;  // block of each unit
+    device_buf<uint32_t> unit_ent;    // its compact-row range
+    device_buf<uint32_t> kptr;        // first entry of each compact row [nkpairs + 1]
+    device_buf<uint32_t> kpos;        // partial slot of each compact row
+    device_buf<uint32_t> rp2;         // row-major offsets of each row's partials [nr_rows + 1]
+    device_buf<uint16_t> rl;          // row-major: chunk-local slot of each partial
+    device_buf<uint32_t> chunk_row;   // row ranges of the merge chunks [nchunks + 1]
+    device_buf<ValueType> part;       // block partials (scratch)
+    uint64_t nkpairs = 0, nchunks = 0;
+    bool xlds = false;                // x block staged in LDS (W * sizeof(V) <= 128 KiB)
+};
+
+// slices (kernel 5, slices.hip): slot-major entries
+struct slices_state {
+    device_buf<ValueType> val;
+    device_scratch off;               // per entry: off_bytes-wide column offsets
+    device_buf<uint32_t> slot_off;    // slots of each 64-row slice [nslices + 1]
+    device_buf<uint32_t> sbase;       // base column of each slot
+    device_buf<uint32_t> len;         // row lengths
+    uint64_t nslices = 0, slots = 0;
+    int off_bytes = 4;                // 1, 2 (offsets from the slot base) or 4 (absolute columns)
+    bool clustered = false;           // 2-byte offsets as (cluster << 14) | offset, 4 bases per slot
+    bool acc_native = false;          // fp32 library: accumulate in fp32 (env SPMV_SLICE_ACC=32)
+    double pad_limit = 0.0;           // automatic choice: give up when stored / real entries exceeds it
+};
+
+// the row panels of the sweep and the binned layouts (y of one panel fits a workgroup's LDS). The
+// one state two layouts share: both cut the same panels, and spmv_hw's streamed copy-back reads
+// them for either.
+struct panels_state {
+    uint64_t npanels = 0;
+    uint64_t ent_pad = 0;             // stored entries, panels (sweep) / segments (binned) padded
+    uint32_t rmax = 0;                // rows of the largest panel
+    device_buf<uint32_t> row;         // first row of each panel [npanels + 1]
+};
+
+// panel sweep (kernel 2, sweep.hip; sweep_multi.hip when nvec > 1)
+struct sweep_state {
+    int variant = 28;                  // sweep-kernel variant (spmv_plan_set_variant)
+    uint64_t nunits = 0;               // workgroups of a launch = npanels * split
+    uint32_t split = 1;                // > 1: some panel is cut into pieces (partials + combine)
+    device_buf<uint32_t> unit_panel;   // panel of each work unit
+    device_buf<uint32_t> panel_unit;   // first unit of each panel [npanels + 1]
+    device_scratch part;               // split > 1: nunits x (panels.rmax + 1) partial sums (accumulator type)
+    double xbias_split = 0.0;          // the pieces' XCC bias in use (split plans; env SPMV_SWEEP_XCC_BIAS)
+    device_buf<unsigned long long> steal;  // tools build, split > 1: per unit, iterations claimed
+                                           // from the front (low word) and back (high word) by the
+                                           // work-stealing variants 37-39; re-armed by k_sweep_combine
+    bool can_steal = false;            // the stealing variants can run on this plan (tools build)
+    device_buf<uint32_t> panel_cnt;    // split > 1 with env SPMV_SWEEP_COMBINE=fused: per-panel count of
+                                       // finished pieces (the last one combines, sweep.hip
+                                       // write_panel); null (default): k_sweep_combine
+    int acc_bytes = 8;                 // LDS accumulator: 8 (fp64) or 4 (fp32 via CAS, env SPMV_SWEEP_ACC=32)
+    int nvec = 1;                      // > 1: spmv_multi's one-pass sweep plan, panels sized for this many
+                                       // accumulators per row, unpacked entries, never split; run only by
+                                       // launch_sweep_multi (sweep_multi.hip)
+    device_buf<uint32_t> col, unit_ent;
+    device_buf<uint16_t> row;
+    device_buf<ValueType> val;
+    device_buf<uint32_t> cbase;      // packed form: base column per 128-entry chunk
+    bool packed = false;
+    bool lane_order = false;         // packed chunks stored in lane order (k_sweep_lane_order)
+    bool det = false;                // env SPMV_SWEEP_DETERMINISTIC=1: ordered LDS adds (k_spmv_sweep_turn)
+    // delta-coded columns (default for packed lane-ordered plans, env SPMV_SWEEP_DELTA=0 off): the
+    // default kernel streams 11 B/entry fp64 (7 fp32) instead of 12 (8); the 12-byte rc words
+    // (col) are freed and rebuilt on demand for the kernels that read them
+    // (sweep_materialize_rc: deterministic variants, variant 35, ablations)
+    device_buf<uint16_t> row16;      // row in panel per entry (bits 0-14) + bit 8 of its delta (lane order)
+    device_buf<uint8_t> d8;          // low 8 bits of the column minus the previous entry's column of
+                                     // the same wave instruction (the first from the chunk base)
+    device_buf<uint32_t> dbase;      // per chunk: base column, or bit 31 | index into side
+    device_buf<uint32_t> side;       // absolute columns (lane order) of chunks with a gap > 511
+    uint64_t side_chunks = 0;
+    bool delta = false;
+    bool wide = false;               // some chunks span >= 65536 columns: their columns live only in
+                                     // the side table (delta plans; no 12-byte rc words can be rebuilt)
+};
+
+// binned (kernel 6, binned.hip): entries ordered (window, panel), segments padded
+struct binned_state {
+    uint32_t nwin = 0, W = 0;          // column windows of W columns (x staged in LDS by pass 1)
+    uint32_t W1 = 0;                   // width of the odd windows (W: the even ones; XCC bias)
+    uint64_t nunits = 0;               // pass-1 work units
+    device_buf<ValueType> val;
+    device_buf<uint16_t> colw;         // column - window base
+    device_scratch rowp;               // u16 row - panel base, or (delta) u8 row deltas
+    bool delta = false;                // segments sorted by row, 1-byte deltas (binned.hip)
+    bool prod_temporal = false;        // pass 1 stores the products with the default cache policy
+                                       // (they stay partly in MALL for pass 2): products <= 1 GiB
+    device_scratch prod_alloc;         // the products' allocation
+    ValueType *prod = nullptr;         // products, written by pass 1 and read by pass 2: a pointer into
+                                       // prod_alloc (it may start past its base), not owned
+    device_buf<uint64_t> seg;          // padded segment offsets [nwin * npanels + 1]
+    device_buf<uint64_t> seg_hi;       // variants 1 / 2 (tests): seg + seg_base, read by pass 2
+    uint64_t seg_base = 0;             // with prod / rowp rebased by -seg_base (same addresses)
+    device_buf<uint64_t> ub;           // pass-1 unit boundaries [nunits + 1]
+    device_buf<uint32_t> uwin;         // window of each pass-1 unit
+    double skew_limit = 0.0;           // automatic choice: give up (rc 2) when a panel holds more than
+                                       // this many times the mean entries (long rows: pass 2 would
+                                       // serialise their LDS adds on one address)
+    double row_limit = 0.0;            // automatic choice: give up (rc 2) when one row holds more than
+                                       // this fraction of a panel's mean entries (same reason; env
+                                       // SPMV_BIN_ROW_LIMIT overrides the automatic value)
+};
+
+// spmv_hw's streamed copy-back (csr_hw_wrapper.cpp): while y_flag is set, the sweep kernel (or
+// binned's pass 2) stores y_epoch into y_flag[panel] (host memory) once the panel's rows of y are
+// in memory. Both pointers are the wrapper's, lent for one run: never freed here.
+struct release_state {
+    uint32_t *y_flag = nullptr;
+    uint32_t y_epoch = 0;
+    ValueType *y_host = nullptr;  // (tools build, SPMV_HW_DIRECT=1) the sweep stores y here instead
+                                  // of d_y: mapped pinned host memory
+};
+
+// spmv_plan_run_graph (graph.cpp): `iters` SpMVs on (x, y) captured once, replayed per call
+struct graph_state {
+    hipGraphExec_t exec = nullptr;
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;  // second capture stream (the tools build's "dag" form: the combines)
+    const ValueType *x = nullptr;   // the caller's vectors the capture holds (not owned)
+    ValueType *y = nullptr;
+    int iters = 0;
+    device_scratch part2;           // split sweep plans: a second partial buffer beside sweep.part, so
+                                    // that step k + 1's sweep can run while step k's partials wait
+                                    // for their combine
+    device_buf<uint32_t> count;     // "behind" form: two chunk counters
+    hipError_t drop_exec()          // a capture made for other vectors, or another variant, must not be replayed
+    {
+        hipGraphExec_t e = exec;
+        exec = nullptr;
+        return e ? hipGraphExecDestroy(e) : hipSuccess;
+    }
+    ~graph_state()  // (not copyable: its buffers are not)
+    {
+        (void)drop_exec();
+        if (stream)
+            (void)hipStreamDestroy(stream);
+        if (stream2)
+            (void)hipStreamDestroy(stream2);
+    }
+};
+
+// timing (HIP events around the main kernel, on the launch stream)
+struct timing_state {
+    bool on = false;
+    std::vector<hipEvent_t> ev;   // pairs
+    size_t used = 0;
+    timing_state() = default;
+    timing_state(const timing_state &) = delete;
+    ~timing_state()
+    {
+        for (hipEvent_t e : ev)
+            (void)hipEventDestroy(e);
+    }
+};
+
 }  // namespace spmvhw
 
 // What a plan knows before any layout is built: plan_create_from_slice fills it once, and every
@@ -81,154 +312,35 @@ struct plan_seed {
     double locality = -1.0;    // probe result used by the automatic kernel choice
 };
 
+// The plan: the seed, which layout it is, and every layout's state (plain members; the unused
+// layouts' are a few dozen null words). The members free themselves; the destructor only waits
+// for the device to be done with them.
 struct spmv_plan : plan_seed {
     spmv_plan() = default;
     explicit spmv_plan(const plan_seed &seed) : plan_seed(seed) {}
-    uint64_t nnz_pad = 0;
-    uint64_t ntiles = 0;
     int kernel = 0;
     int op = SPMV_OP_N;        // SPMV_OP_T: the plan holds A^T of the slice it was created from
-    int variant = 0;           // tile-kernel variant bits (spmv_plan_set_variant)
-    int sweep_variant = 28;    // sweep-kernel variant bits (spmv_plan_set_variant, kernel 2)
-
-    uint32_t *d_col = nullptr;
-    void *d_colnar = nullptr;        // narrow form: u16 or u8 offsets from tile_cbase (d_col freed)
-    uint32_t *d_tile_cbase = nullptr;
-    int tile_col_bytes = 4;          // 4 (d_col), 2 or 1 (d_colnar)
-    bool tile_clustered = false;     // 2-byte columns as (cluster << 14) | offset, 4 bases per tile
-    bool tile_xcd = false;           // XCD-contiguous tile order (env SPMV_TILE_XCD=1); measured
-                                     // slower on stencils (+6 %), 2 % faster on banded
-    ValueType *d_val = nullptr;
-    uint32_t *d_rowend = nullptr;
-    uint32_t *d_tile_info = nullptr;
-    uint32_t *d_row_id = nullptr;
-    ValueType *d_head = nullptr;
-    ValueType *d_tail = nullptr;
-    uint32_t *d_cross = nullptr;   // rows crossing tile boundaries: (row, first tile, last tile)
-    uint64_t ncross = 0;
-
-    // gold-order representation (kernel 1, gold.hip): plain CSR in d_rp / d_col / d_val
-    uint32_t *d_rp = nullptr;         // rebased row_ptr[nr_rows + 1]
-    uint64_t nlong = 0;               // rows with more than kGoldLong entries (stats)
-    int fpga_vf = 1;                  // kernel 3: vectorisation factor (env SPMV_FPGA_VF)
-    uint32_t fpga_width = 32768;      // kernel 3: column-block width (env SPMV_FPGA_BLOCK)
-
-    // blocked representation (kernel 4, blocked.hip): entries by (block, row) in d_val (values)
-    // and d_colnar (u16 block-relative columns); units in d_unit_panel (block) / d_unit_ent
-    // (compact-row ranges)
-    uint32_t *d_kptr = nullptr;       // first entry of each compact row [nkpairs + 1]
-    uint32_t *d_kpos = nullptr;       // partial slot of each compact row
-    uint32_t *d_rp2 = nullptr;        // row-major offsets of each row's partials [nr_rows + 1]
-    uint16_t *d_rl = nullptr;         // row-major: chunk-local slot of each partial
-    uint32_t *d_chunk_row = nullptr;  // row ranges of the merge chunks [nchunks + 1]
-    ValueType *d_bpart = nullptr;     // block partials (scratch)
-    uint64_t nkpairs = 0, nchunks = 0;
-    bool blocked_xlds = false;        // x block staged in LDS (W * sizeof(V) <= 128 KiB)
-
-    // slice representation (kernel 5, slices.hip): slot-major entries in d_val / d_colnar
-    uint32_t *d_slot_off = nullptr;   // slots of each 64-row slice [nslices + 1]
-    uint32_t *d_sbase = nullptr;      // base column of each slot
-    uint32_t *d_slice_len = nullptr;  // row lengths
-    uint64_t nslices = 0, slice_slots = 0;
-    int slice_off_bytes = 4;          // 1, 2 (offsets from the slot base) or 4 (absolute columns)
-    bool slice_clustered = false;     // 2-byte offsets as (cluster << 14) | offset, 4 bases per slot
-    bool slice_acc_native = false;    // fp32 library: accumulate in fp32 (env SPMV_SLICE_ACC=32)
-    double slice_pad_limit = 0.0;     // automatic choice: give up when stored / real entries exceeds it
-
-    // panel-sweep representation (kernel 2, sweep.hip)
-    uint64_t npanels = 0, ent_pad = 0;
-    uint64_t nunits = 0;               // workgroups of a launch = npanels * sweep_split
-    uint32_t sweep_split = 1;          // > 1: some panel is cut into pieces (partials + combine)
-    uint32_t *d_unit_panel = nullptr;  // panel of each work unit
-    uint32_t *d_panel_unit = nullptr;  // first unit of each panel [npanels + 1]
-    void *d_part = nullptr;            // split > 1: nunits x (panel_rmax + 1) partial sums (accumulator type)
-    std::vector<void *> gpart;         // spmv_plan_run_graph: a second partial buffer beside d_part, so
-                                       // that step k + 1's sweep can run while step k's partials wait
-                                       // for their combine
-    uint32_t *d_gcount = nullptr;      // spmv_plan_run_graph, "behind" form: two chunk counters
-    double xbias_split = 0.0;          // the pieces' XCC bias in use (split plans; env SPMV_SWEEP_XCC_BIAS)
-    unsigned long long *d_steal = nullptr;  // tools build, split > 1: per unit, iterations claimed
-                                            // from the front (low word) and back (high word) by the
-                                            // work-stealing variants 37-39; re-armed by k_sweep_combine
-    bool sweep_steal = false;          // the stealing variants can run on this plan (tools build)
-    uint32_t *d_panel_cnt = nullptr;   // split > 1 with env SPMV_SWEEP_COMBINE=fused: per-panel count of
-                                       // finished pieces (the last one combines, sweep.hip
-                                       // write_panel); null (default): k_sweep_combine
-    int sweep_acc_bytes = 8;           // LDS accumulator: 8 (fp64) or 4 (fp32 via CAS, env SPMV_SWEEP_ACC=32)
-    uint32_t panel_rmax = 0;
-    int sweep_nvec = 1;             // > 1: spmv_multi's one-pass sweep plan, panels sized for this many
-                                     // accumulators per row, unpacked entries, never split; run only by
-                                     // launch_sweep_multi (sweep_multi.hip)
-    uint32_t *d_s_col = nullptr;
-    uint16_t *d_s_row = nullptr;
-    ValueType *d_s_val = nullptr;
-    uint32_t *d_panel_row = nullptr;
-    uint32_t *d_unit_ent = nullptr;
-    uint32_t *d_s_cbase = nullptr;   // packed form: base column per 128-entry chunk
-    bool sweep_packed = false;
-    bool sweep_lane_order = false;   // packed chunks stored in lane order (k_sweep_lane_order)
-    bool sweep_det = false;          // env SPMV_SWEEP_DETERMINISTIC=1: ordered LDS adds (k_spmv_sweep_turn)
-    // delta-coded columns (default for packed lane-ordered plans, env SPMV_SWEEP_DELTA=0 off): the
-    // default kernel streams 11 B/entry fp64 (7 fp32) instead of 12 (8); the 12-byte rc words
-    // (d_s_col) are freed and rebuilt on demand for the kernels that read them
-    // (sweep_materialize_rc: deterministic variants, variant 35, ablations)
-    uint16_t *d_s_row16 = nullptr;   // row in panel per entry (bits 0-14) + bit 8 of its delta (lane order)
-    uint8_t *d_s_d8 = nullptr;       // low 8 bits of the column minus the previous entry's column of
-                                     // the same wave instruction (the first from the chunk base)
-    uint32_t *d_s_dbase = nullptr;   // per chunk: base column, or bit 31 | index into d_s_side
-    uint32_t *d_s_side = nullptr;    // absolute columns (lane order) of chunks with a gap > 511
-    uint64_t sweep_side_chunks = 0;
-    bool sweep_delta = false;
-    bool sweep_wide = false;         // some chunks span >= 65536 columns: their columns live only in
-                                     // the side table (delta plans; no 12-byte rc words can be rebuilt)
-    // binned representation (kernel 6, binned.hip): reuses npanels, panel_rmax, d_panel_row and
-    // ent_pad of the sweep fields; entries ordered (window, panel), segments padded
-    uint32_t b_nwin = 0, b_W = 0;      // column windows of b_W columns (x staged in LDS by pass 1)
-    uint32_t b_W1 = 0;                 // width of the odd windows (b_W: the even ones; XCC bias)
-    uint64_t b_nunits = 0;             // pass-1 work units
-    ValueType *d_b_val = nullptr;
-    uint16_t *d_b_colw = nullptr;      // column - window base
-    void *d_b_rowp = nullptr;          // u16 row - panel base, or (b_delta) u8 row deltas
-    bool b_delta = false;              // segments sorted by row, 1-byte deltas (binned.hip)
-    bool b_prod_temporal = false;      // pass 1 stores the products with the default cache policy
-                                       // (they stay partly in MALL for pass 2): products <= 1 GiB
-    ValueType *d_b_prod = nullptr;     // products, written by pass 1 and read by pass 2
-    void *d_b_prod_alloc = nullptr;    // its allocation (d_b_prod may start past its base)
-    uint64_t *d_b_seg = nullptr;       // padded segment offsets [b_nwin * npanels + 1]
-    uint64_t *d_b_seg_hi = nullptr;    // variants 1 / 2 (tests): d_b_seg + b_seg_base, read by pass 2
-    uint64_t b_seg_base = 0;           // with prod / rowp rebased by -b_seg_base (same addresses)
-    uint64_t *d_b_ub = nullptr;        // pass-1 unit boundaries [b_nunits + 1]
-    uint32_t *d_b_uwin = nullptr;      // window of each pass-1 unit
-    double bin_skew_limit = 0.0;       // automatic choice: give up (rc 2) when a panel holds more than
-                                       // this many times the mean entries (long rows: pass 2 would
-                                       // serialise their LDS adds on one address)
-    double bin_row_limit = 0.0;        // automatic choice: give up (rc 2) when one row holds more than
-                                       // this fraction of a panel's mean entries (same reason; env
-                                       // SPMV_BIN_ROW_LIMIT overrides the automatic value)
-    // spmv_hw's streamed copy-back (csr_hw_wrapper.cpp): while set, the sweep kernel stores
-    // y_epoch into y_flag[panel] (host memory) once the panel's rows of y are in memory
-    uint32_t *y_flag = nullptr;
-    uint32_t y_epoch = 0;
-    ValueType *y_host = nullptr;  // (tools build, SPMV_HW_DIRECT=1) the sweep stores y here instead
-                                  // of d_y: mapped pinned host memory
+    int variant = 0;           // variant bits of every layout but the sweep (spmv_plan_set_variant)
     double tuned_ms[4] = {-1.0, -1.0, -1.0, -1.0};  // SPMV_HW_KERNEL=tune: tiles / sweep / slices / binned ms
 
-    // timing (HIP events around the main kernel, on the launch stream)
-    bool timing = false;
-    std::vector<hipEvent_t> ev;   // pairs
-    size_t ev_used = 0;
-
-    // spmv_plan_run_graph: `giters` SpMVs on (gx, gy) captured once, replayed per call
-    hipGraphExec_t gexec = nullptr;
-    hipStream_t gstream = nullptr;
-    hipStream_t gstream2 = nullptr;  // second capture stream (the tools build's "dag" form: the combines)
-    const ValueType *gx = nullptr;
-    ValueType *gy = nullptr;
-    int giters = 0;
+    spmvhw::tiles_state tiles;
+    spmvhw::csr_state csr;
+    spmvhw::blocked_state blocked;
+    spmvhw::slices_state slices;
+    spmvhw::panels_state panels;
+    spmvhw::sweep_state sweep;
+    spmvhw::binned_state binned;
+    spmvhw::release_state release;
+    spmvhw::graph_state graph;
+    spmvhw::timing_state timing;
 
     uint64_t device_bytes() const;
     uint64_t algorithmic_bytes() const;
-    ~spmv_plan();  // frees every device buffer and event (also on error paths)
+    ~spmv_plan()  // (also on error paths)
+    {
+        (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();
+    }
 };
 
 namespace spmvhw {
@@ -272,7 +384,10 @@ struct layout_ops {
     int tune_slot;                             // index into spmv_plan::tuned_ms; -1: not a tune candidate
     int product_variants[2];                   // what the product library accepts beside 0 (0: nothing more)
     int (*set_variant)(spmv_plan &p, int variant);  // 0, or 1 with the error set
-    bool host_y;                               // the kernel can store y to spmv_plan::y_host (tools build)
+    bool host_y;                               // the kernel can store y to release.y_host (tools build)
+    // the plan as it stands (its variant included) writes y panel by panel and can flag each panel
+    // as it is stored (release.y_flag: spmv_hw's streamed copy-back); null: the layout never can
+    bool (*flags_panels)(const spmv_plan &p);
 };
 const layout_ops &tiles_layout(), &gold_layout(), &sweep_layout(), &fpga_layout(), &blocked_layout(), &slices_layout(),
     &binned_layout();
@@ -319,7 +434,7 @@ hipError_t launch_narrow(const uint32_t *d_col, uint64_t nnz, uint64_t nnz_pad, 
 
 // gold.hip
 hipError_t launch_gold(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm = false);
-int fpga_params(spmv_plan &p);  // fpga_vf / fpga_width from env SPMV_FPGA_VF / SPMV_FPGA_BLOCK (kernels 3 and 4)
+int fpga_params(spmv_plan &p);  // csr.fpga_vf / csr.fpga_width from env SPMV_FPGA_VF / SPMV_FPGA_BLOCK (kernels 3 and 4)
 
 // blocked.hip
 hipError_t launch_blocked(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm = false);
@@ -342,7 +457,7 @@ int build_binned(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src
 
 // sweep.hip
 // phase 0: the sweep and (split plans) the combine; 1: the sweep only; 2: the combine only.
-// part: the partial-sum buffer of a split plan (null: the plan's own d_part)
+// part: the partial-sum buffer of a split plan (null: the plan's own sweep.part)
 // behind: (spmv_plan_run_graph of a split plan) the previous step's combine, run by extra blocks
 // of this sweep launch (sweep.hip, combine_behind); only where sweep_behind_ok
 struct sweep_behind {
@@ -360,47 +475,13 @@ int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src,
                 hipStream_t s);
 int probe_locality(const IndexType *d_rp, const IndexType *d_col, IndexType n, hipStream_t s, double *frac);
 int sweep_materialize_rc(spmv_plan &p);  // delta plan: rebuild the 12-byte rc words (once)
-// the plan's default launch is the packed sweep with one workgroup per panel (no combine), whose
-// workgroups can flag each panel's y as it is stored (spmv_plan::y_flag)
-bool sweep_can_flag_panels(const spmv_plan &p);
 
 // sweep_multi.hip
-// K = nvec (2, 4 or 8) right-hand sides in one pass over a sweep plan built with sweep_nvec = nvec;
+// K = nvec (2, 4 or 8) right-hand sides in one pass over a sweep plan built with sweep.nvec = nvec;
 // X and Y row-major. Enqueues only the kernel (capturable)
 hipError_t launch_sweep_multi(const spmv_plan &p, int nvec, const ValueType *d_X, ValueType *d_Y, hipStream_t s,
                               bool warm = false);
 
-// device scratch of a build step, freed on scope exit
-struct device_scratch {
-    void *p = nullptr;
-    ~device_scratch()
-    {
-        if (p)
-            (void)hipFree(p);
-    }
-};
-// ... of `count` elements of T. release() frees early (where that bounds a build's peak memory);
-// swap() trades the buffer with one the plan owns, so the scratch frees what the plan held
-template <typename T>
-struct device_buf : device_scratch {
-    device_buf() = default;
-    device_buf(const device_buf &) = delete;  // one owner (a kernel argument is get(), never the buffer)
-    T *get() const { return static_cast<T *>(p); }
-    operator T *() const { return get(); }
-    hipError_t alloc(uint64_t count) { return hipMalloc(&p, count * sizeof(T)); }
-    hipError_t release()
-    {
-        void *q = p;
-        p = nullptr;
-        return q ? hipFree(q) : hipSuccess;
-    }
-    void swap(T *&owned)
-    {
-        T *q = get();
-        p = owned;
-        owned = q;
-    }
-};
 // a kernel over `items` threads in blocks of `block`; the launch's error
 template <typename K, typename... Args>
 inline hipError_t launch_items(K kernel, uint64_t items, unsigned block, hipStream_t s, Args... args)
@@ -447,9 +528,9 @@ int slice_entries_on_device(const csr_slice &sl, device_scratch &up_col, device_
 // plan.cpp: the plan of the slice (op = SPMV_OP_T: of its device transpose, transpose_slice, the plan's op set).
 // force_kernel >= 0: that kernel as if env SPMV_HW_KERNEL named it (spmv_multi's slice path).
 // multi_nvec > 1 (spmv_multi's one-pass sweep), with force_kernel = -1: the sweep plan is built
-// with that many accumulators per row (spmv_plan::sweep_nvec) when the automatic choice for the
+// with that many accumulators per row (sweep.nvec) when the automatic choice for the
 // matrix is the sweep or the binned kernel, the unsplit panels fill a round of workgroups and
-// the build does not decline -- otherwise the plan is the ordinary one (sweep_nvec = 1), exactly
+// the build does not decline -- otherwise the plan is the ordinary one (sweep.nvec = 1), exactly
 // as without the argument.
 int plan_create_from_slice(spmv_plan **out, int device, int op, const csr_slice &sl, int force_kernel = -1,
                            int multi_nvec = 1);

@@ -1081,17 +1081,17 @@ __global__ void k_sweep_delta_decode(const uint16_t *__restrict__ row16, const u
 // deterministic variants 91 / 94, variant 35, the ablations) gets them rebuilt here, once
 int sweep_materialize_rc(spmv_plan &p)
 {
-    if (!p.sweep_delta || p.d_s_col || p.ent_pad == 0)
+    if (!p.sweep.delta || p.sweep.col.get() || p.panels.ent_pad == 0)
         return 0;
-    if (p.sweep_wide) {  // chunks spanning >= 65536 columns have no 16-bit offsets
+    if (p.sweep.wide) {  // chunks spanning >= 65536 columns have no 16-bit offsets
         set_error("sweep variant needs the 12-byte entries, which this plan's wide chunks cannot hold");
         return 1;
     }
-    const uint64_t nchunks = p.ent_pad / kSweepChunk;
+    const uint64_t nchunks = p.panels.ent_pad / kSweepChunk;
     SPMV_TRY(hipSetDevice(p.device));
-    SPMV_TRY(hipMalloc((void **)&p.d_s_col, p.ent_pad * 4));
-    hipLaunchKernelGGL(k_sweep_delta_decode, dim3((unsigned)((nchunks + 63) / 64)), dim3(64), 0, nullptr, p.d_s_row16,
-                       p.d_s_d8, p.d_s_dbase, p.d_s_cbase, p.d_s_side, nchunks, p.d_s_col);
+    SPMV_TRY(p.sweep.col.alloc(p.panels.ent_pad));
+    hipLaunchKernelGGL(k_sweep_delta_decode, dim3((unsigned)((nchunks + 63) / 64)), dim3(64), 0, nullptr, p.sweep.row16.get(),
+                       p.sweep.d8.get(), p.sweep.dbase.get(), p.sweep.cbase.get(), p.sweep.side.get(), nchunks, p.sweep.col.get());
     SPMV_TRY(hipGetLastError());
     SPMV_TRY(hipDeviceSynchronize());
     return 0;
@@ -1199,76 +1199,79 @@ template <int T, typename A>
 static void launch_sweep_t(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm,
                            void *part_buf, const sweep_behind &bh)
 {
-    const size_t lds = (size_t(p.panel_rmax) + 1) * sizeof(A);
-    const dim3 grid((unsigned)p.nunits), block(T);
-    const dim3 gridb((unsigned)p.nunits + (bh.cpart ? bh.blocks : 0u));  // + the combine behind
+    const sweep_state &w = p.sweep;
+    const panels_state &pn = p.panels;
+    const release_state &rel = p.release;
+    const size_t lds = (size_t(pn.rmax) + 1) * sizeof(A);
+    const dim3 grid((unsigned)w.nunits), block(T);
+    const dim3 gridb((unsigned)w.nunits + (bh.cpart ? bh.blocks : 0u));  // + the combine behind
     A *part = reinterpret_cast<A *>(part_buf);
-    uint32_t *pcnt = p.sweep_split > 1 && p.d_panel_cnt ? p.d_panel_cnt : nullptr;  // fused combine
+    uint32_t *pcnt = w.split > 1 && w.panel_cnt.get() ? w.panel_cnt.get() : nullptr;  // fused combine
     // Unpacked (14-B entries, used when a chunk spans >= 65536 columns): E entries per thread,
     // Q groups per barrier, SYNC barrier, NT non-temporal entry loads.
 #define SWEEP(E, Q, SYNC, NT)                                                                     \
-    launch_or_warm(warm, k_spmv_sweep<ValueType, T, E, Q, SYNC, NT, A>, grid, block, lds, s, p.d_s_col,   \
-                       p.d_s_row, p.d_s_val, p.d_panel_row, p.d_unit_ent, p.d_unit_panel, p.d_panel_unit, part, p.panel_rmax + 1, pcnt, d_x, d_y)
+    launch_or_warm(warm, k_spmv_sweep<ValueType, T, E, Q, SYNC, NT, A>, grid, block, lds, s, w.col.get(),   \
+                       w.row.get(), w.val.get(), pn.row.get(), w.unit_ent.get(), w.unit_panel.get(), w.panel_unit.get(), part, pn.rmax + 1, pcnt, d_x, d_y)
     // deterministic form (env SPMV_SWEEP_DETERMINISTIC=1, or variants 91 / 94 on any sweep plan)
 #define TURN(PK, ORD)                                                                              \
-    launch_or_warm(warm, k_spmv_sweep_turn<ValueType, T, 2, PK, ORD, A>, grid, block, lds, s, p.d_s_col,          \
-                   p.d_s_cbase, p.d_s_row, p.d_s_val, p.d_panel_row, p.d_unit_ent, p.d_unit_panel, p.d_panel_unit, \
-                   part, p.panel_rmax + 1, pcnt, d_x, d_y)
+    launch_or_warm(warm, k_spmv_sweep_turn<ValueType, T, 2, PK, ORD, A>, grid, block, lds, s, w.col.get(),          \
+                   w.cbase.get(), w.row.get(), w.val.get(), pn.row.get(), w.unit_ent.get(), w.unit_panel.get(), w.panel_unit.get(), \
+                   part, pn.rmax + 1, pcnt, d_x, d_y)
 #ifdef SPMV_ABLATIONS
     // measurement only: the turn kernel's pipeline without the ordering (52: loose sync, 51: none)
-    if (p.sweep_packed && p.sweep_variant == 52) {
+    if (w.packed && w.variant == 52) {
         TURN(true, 2);
         return;
     }
-    if (p.sweep_packed && p.sweep_variant == 51) {
+    if (w.packed && w.variant == 51) {
         TURN(true, 3);
         return;
     }
 #endif
-    if (p.sweep_det || p.sweep_variant == kSweepTurn || p.sweep_variant == kSweepTurnOrdered) {
+    if (w.det || w.variant == kSweepTurn || w.variant == kSweepTurnOrdered) {
         // ORD 0 (each wave's adds complete before the release hand-over) is the default of
         // SPMV_SWEEP_DETERMINISTIC=1: its ordering follows from the memory model alone. Variant 91
         // (tools library) keeps the 3 % faster ORD 1 hand-over (compiler ordering; relies on the
         // LDS executing a CU's requests in arrival order) for measurements.
 #ifdef SPMV_ABLATIONS
-        if (p.sweep_variant == kSweepTurn) {
-            if (p.sweep_packed) TURN(true, 1); else TURN(false, 1);
+        if (w.variant == kSweepTurn) {
+            if (w.packed) TURN(true, 1); else TURN(false, 1);
             return;
         }
 #endif
-        if (p.sweep_packed) TURN(true, 0); else TURN(false, 0);
+        if (w.packed) TURN(true, 0); else TURN(false, 0);
         return;
     }
 #undef TURN
-    if (p.sweep_packed) {
+    if (w.packed) {
 #define PKN(NT, Q, LAG, ABL)                                                                        \
-    launch_or_warm(warm, k_spmv_sweep_packed<ValueType, T, Q, NT, LAG, ABL, A>, grid, block, lds, s, p.d_s_col, \
-                       p.d_s_cbase, p.d_s_val, p.d_panel_row, p.d_unit_ent, p.d_unit_panel, p.d_panel_unit, part, p.panel_rmax + 1, pcnt, d_x, d_y, \
+    launch_or_warm(warm, k_spmv_sweep_packed<ValueType, T, Q, NT, LAG, ABL, A>, grid, block, lds, s, w.col.get(), \
+                       w.cbase.get(), w.val.get(), pn.row.get(), w.unit_ent.get(), w.unit_panel.get(), w.panel_unit.get(), part, pn.rmax + 1, pcnt, d_x, d_y, \
                        (const uint16_t *)nullptr, (const uint8_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, \
-                       (unsigned long long *)nullptr, 0u, (uint32_t)p.nunits, (const A *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, 0u)
+                       (unsigned long long *)nullptr, 0u, (uint32_t)w.nunits, (const A *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, 0u)
     // the default kernel on delta-coded columns (variant 28's loose sync: 2 groups, lag 2)
 #define PKD(ST, TAIL)                                                                                 \
-    launch_or_warm(warm, k_spmv_sweep_packed<ValueType, T, 2, true, 2, 0, A, true, ST>, gridb, block, lds, s, p.d_s_col, \
-                       p.d_s_cbase, p.d_s_val, p.d_panel_row, p.d_unit_ent, p.d_unit_panel, p.d_panel_unit, part, p.panel_rmax + 1, pcnt, d_x, d_y, \
-                       p.d_s_row16, p.d_s_d8, p.d_s_dbase, p.d_s_side, ST ? p.d_steal : (unsigned long long *)nullptr, (uint32_t)(TAIL), \
-                       (uint32_t)p.nunits, reinterpret_cast<const A *>(bh.cpart), bh.ccount, bh.cnext, (uint32_t)p.npanels, bh.rows_per_thread)
-    // spmv_hw's streamed copy-back (p.y_flag set: plans of one piece per panel, default variant)
+    launch_or_warm(warm, k_spmv_sweep_packed<ValueType, T, 2, true, 2, 0, A, true, ST>, gridb, block, lds, s, w.col.get(), \
+                       w.cbase.get(), w.val.get(), pn.row.get(), w.unit_ent.get(), w.unit_panel.get(), w.panel_unit.get(), part, pn.rmax + 1, pcnt, d_x, d_y, \
+                       w.row16.get(), w.d8.get(), w.dbase.get(), w.side.get(), ST ? w.steal.get() : (unsigned long long *)nullptr, (uint32_t)(TAIL), \
+                       (uint32_t)w.nunits, reinterpret_cast<const A *>(bh.cpart), bh.ccount, bh.cnext, (uint32_t)pn.npanels, bh.rows_per_thread)
+    // spmv_hw's streamed copy-back (rel.y_flag set: plans of one piece per panel, default variant)
 #define PKDF()                                                                                        \
     launch_or_warm(warm, k_spmv_sweep_packed<ValueType, T, 2, true, 2, 0, A, true, false, uint32_t *, uint32_t, ValueType *>, gridb, block, lds, s, \
-                   p.d_s_col, p.d_s_cbase, p.d_s_val, p.d_panel_row, p.d_unit_ent, p.d_unit_panel, p.d_panel_unit, part, \
-                   p.panel_rmax + 1, pcnt, d_x, d_y, p.d_s_row16, p.d_s_d8, p.d_s_dbase, p.d_s_side,               \
-                   (unsigned long long *)nullptr, 0u, (uint32_t)p.nunits, (const A *)nullptr, (uint32_t *)nullptr,  \
-                   (uint32_t *)nullptr, (uint32_t)p.npanels, 0u, p.y_flag, p.y_epoch, p.y_host)
+                   w.col.get(), w.cbase.get(), w.val.get(), pn.row.get(), w.unit_ent.get(), w.unit_panel.get(), w.panel_unit.get(), part, \
+                   pn.rmax + 1, pcnt, d_x, d_y, w.row16.get(), w.d8.get(), w.dbase.get(), w.side.get(),               \
+                   (unsigned long long *)nullptr, 0u, (uint32_t)w.nunits, (const A *)nullptr, (uint32_t *)nullptr,  \
+                   (uint32_t *)nullptr, (uint32_t)pn.npanels, 0u, rel.y_flag, rel.y_epoch, rel.y_host)
 #define PKF()                                                                                         \
-    launch_or_warm(warm, k_spmv_sweep_packed<ValueType, T, 2, true, 2, 0, A, false, false, uint32_t *, uint32_t, ValueType *>, grid, block, lds, s, p.d_s_col, \
-                   p.d_s_cbase, p.d_s_val, p.d_panel_row, p.d_unit_ent, p.d_unit_panel, p.d_panel_unit, part,        \
-                   p.panel_rmax + 1, pcnt, d_x, d_y, (const uint16_t *)nullptr, (const uint8_t *)nullptr,           \
+    launch_or_warm(warm, k_spmv_sweep_packed<ValueType, T, 2, true, 2, 0, A, false, false, uint32_t *, uint32_t, ValueType *>, grid, block, lds, s, w.col.get(), \
+                   w.cbase.get(), w.val.get(), pn.row.get(), w.unit_ent.get(), w.unit_panel.get(), w.panel_unit.get(), part,        \
+                   pn.rmax + 1, pcnt, d_x, d_y, (const uint16_t *)nullptr, (const uint8_t *)nullptr,           \
                    (const uint32_t *)nullptr, (const uint32_t *)nullptr, (unsigned long long *)nullptr, 0u,          \
-                   (uint32_t)p.nunits, (const A *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, 0u,        \
-                   p.y_flag, p.y_epoch, p.y_host)
+                   (uint32_t)w.nunits, (const A *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, 0u,        \
+                   rel.y_flag, rel.y_epoch, rel.y_host)
 #define PK(Q, LAG) PKN(true, Q, LAG, 0)
 #define PKA(ABL) PKN(true, 2, 2, ABL)
-        switch (p.sweep_variant) {
+        switch (w.variant) {
 #ifdef SPMV_ABLATIONS
         // measurement variants (tools library): 15/20/22: 2/4/8 groups per barrier; 26-34: loose
         // sync, Q groups, lag (the default is 28: 2 groups, lag 2); 35: the default on the
@@ -1297,25 +1300,25 @@ static void launch_sweep_t(const spmv_plan &p, const ValueType *d_x, ValueType *
         case 57: PKA(6); break;  // x gathers with the nt bit
         case 58: PKA(7); break;  // x gathers that bypass L1 (sc1)
         case 53: PKA(10); break;  // half the value bytes: 8 B/entry streamed instead of 12
-        case 50: if (p.panel_rmax >= 16384) { PKA(11); } else { PK(2, 2); } break;  // 11-B entries + delta decode
+        case 50: if (pn.rmax >= 16384) { PKA(11); } else { PK(2, 2); } break;  // 11-B entries + delta decode
 #endif
         default:
-            if (p.sweep_delta) {
+            if (w.delta) {
 #ifdef SPMV_ABLATIONS
                 // measurement build: work stealing among a panel's pieces on split plans (the
                 // last quarter / half / all of each piece's iterations claimable: variants 39 / 37
                 // / 38). Measured 3.5-5.5 % slower than the static split at N = 4 and N = 8
                 // (profiles/r04c_steal_ab.jsonl), so the product keeps the static split
-                if (p.sweep_steal && (p.sweep_variant == 37 || p.sweep_variant == 38 || p.sweep_variant == 39)) {
-                    PKD(true, p.sweep_variant == 37 ? 8 : p.sweep_variant == 38 ? 16 : 4);
+                if (w.can_steal && (w.variant == 37 || w.variant == 38 || w.variant == 39)) {
+                    PKD(true, w.variant == 37 ? 8 : w.variant == 38 ? 16 : 4);
                     break;
                 }
 #endif
-                if (p.y_flag || warm) PKDF();  // (warm: load the flagged code object too)
-                if (!p.y_flag) PKD(false, 0);
+                if (rel.y_flag || warm) PKDF();  // (warm: load the flagged code object too)
+                if (!rel.y_flag) PKD(false, 0);
             } else {
-                if (p.y_flag || warm) PKF();
-                if (!p.y_flag) PK(2, 2);
+                if (rel.y_flag || warm) PKF();
+                if (!rel.y_flag) PK(2, 2);
             }
             break;
         }
@@ -1327,7 +1330,7 @@ static void launch_sweep_t(const spmv_plan &p, const ValueType *d_x, ValueType *
 #undef PKN
         return;
     }
-    switch (p.sweep_variant) {
+    switch (w.variant) {
 #ifdef SPMV_ABLATIONS
     case 40: SWEEP(4, 1, false, false); break;  // measurement variants of the unpacked form
     case 1: SWEEP(4, 1, false, true); break;
@@ -1341,27 +1344,27 @@ static void launch_sweep_t(const spmv_plan &p, const ValueType *d_x, ValueType *
 #undef SWEEP
 }
 
-// the variants launch_sweep_t sends to the default delta kernel (PKD(false, 0)), split plans
-// with the combine kernel: those whose launch can carry the previous step's combine
-bool sweep_can_flag_panels(const spmv_plan &p)
+// the plan's launch is the default packed sweep with one workgroup per panel (no combine), whose
+// workgroups can flag each panel's y as it is stored (release.y_flag; PKDF / PKF above)
+static bool sweep_flags_panels(const spmv_plan &p)
 {
-    if (p.kernel == kKernelBinned)  // pass 2 writes whole panels too (binned.hip k_bin_acc); not
-        return p.npanels > 0 && p.variant != 51 && p.variant != 52;  // its ablations
-    return p.kernel == kKernelSweep && p.sweep_packed && !p.sweep_det && p.sweep_split == 1 && p.npanels > 0 &&
-           (p.sweep_variant == 0 || p.sweep_variant == 28);
+    return p.sweep.packed && !p.sweep.det && p.sweep.split == 1 && p.panels.npanels > 0 &&
+           (p.sweep.variant == 0 || p.sweep.variant == 28);
 }
 
+// the variants launch_sweep_t sends to the default delta kernel (PKD(false, 0)), split plans
+// with the combine kernel: those whose launch can carry the previous step's combine
 bool sweep_behind_ok(const spmv_plan &p)
 {
     // (packed, delta-coded entries: only build_sweep makes them, so any other layout's plan says no)
-    if (!p.sweep_packed || !p.sweep_delta || p.sweep_det || p.sweep_split < 2 || p.d_panel_cnt)
+    if (!p.sweep.packed || !p.sweep.delta || p.sweep.det || p.sweep.split < 2 || p.sweep.panel_cnt.get())
         return false;
-    switch (p.sweep_variant) {
+    switch (p.sweep.variant) {
     case 15: case 20: case 22: case 26: case 27: case 29: case 30: case 31: case 32: case 33: case 34:
     case 35: case 37: case 38: case 39: case kSweepTurn: case kSweepTurnOrdered:
         return false;
     default:
-        return !(p.sweep_variant >= 50 && p.sweep_variant <= 63);
+        return !(p.sweep.variant >= 50 && p.sweep.variant <= 63);
     }
 }
 
@@ -1376,26 +1379,26 @@ static void launch_sweep_a(const spmv_plan &p, const ValueType *d_x, ValueType *
         default: launch_sweep_t<1024, A>(p, d_x, d_y, s, warm, part, bh); break;
         }
     }
-    if (phase != 1 && p.sweep_split > 1 && !p.d_panel_cnt) {  // the combine kernel (not the fused form)
-        const dim3 grid((p.panel_rmax + 255) / 256, (unsigned)p.npanels);
-        launch_or_warm(warm, k_sweep_combine<ValueType, A>, grid, dim3(256), 0, s, p.d_panel_row, p.d_panel_unit,
-                       reinterpret_cast<const A *>(part), p.panel_rmax + 1, d_y, p.d_steal);
+    if (phase != 1 && p.sweep.split > 1 && !p.sweep.panel_cnt.get()) {  // the combine kernel (not the fused form)
+        const dim3 grid((p.panels.rmax + 255) / 256, (unsigned)p.panels.npanels);
+        launch_or_warm(warm, k_sweep_combine<ValueType, A>, grid, dim3(256), 0, s, p.panels.row.get(), p.sweep.panel_unit.get(),
+                       reinterpret_cast<const A *>(part), p.panels.rmax + 1, d_y, p.sweep.steal.get());
     }
 }
 
 hipError_t launch_sweep(const spmv_plan &p, const ValueType *d_x, ValueType *d_y, hipStream_t s, bool warm, int phase,
                         void *part, const sweep_behind *behind)
 {
-    if (p.npanels == 0)
+    if (p.panels.npanels == 0)
         return hipSuccess;
     if (!part)
-        part = p.d_part;
+        part = p.sweep.part.p;
     const sweep_behind none{};
     if (behind && (behind->cpart || behind->cnext) && !sweep_behind_ok(p))
         return hipErrorNotSupported;
     const sweep_behind &bh = behind ? *behind : none;
     if constexpr (sizeof(ValueType) == 4) {
-        if (p.sweep_acc_bytes == 4) {
+        if (p.sweep.acc_bytes == 4) {
             launch_sweep_a<float>(p, d_x, d_y, s, warm, phase, part, bh);
             return hipGetLastError();
         }
@@ -1413,8 +1416,8 @@ static int sweep_sort_entries(spmv_plan &p, const sweep_units &u, const IndexTyp
 {
     const IndexType n = p.nr_rows;
     const uint64_t nnz = p.nnz;
-    const uint32_t S = (uint32_t)p.npanels;     // sort segments = the panels
-    const uint32_t *d_srow = p.d_panel_row;     // their rows
+    const uint32_t S = (uint32_t)p.panels.npanels;     // sort segments = the panels
+    const uint32_t *d_srow = p.panels.row.get();  // their rows
     // bucket shift so that S * buckets fits 32-bit keys
     uint32_t shift = 0;
     while ((uint64_t(S) * ((uint64_t(p.nr_cols) >> shift) + 1)) >= (1ull << 32))
@@ -1450,28 +1453,28 @@ static int sweep_sort_entries(spmv_plan &p, const sweep_units &u, const IndexTyp
         SPMV_BUILD_TRY(tmp.alloc(tmp_bytes));
         SPMV_BUILD_TRY(sort(tmp.p));
         SPMV_BUILD_TRY(launch_items(k_sweep_scatter<ValueType>, nnz, 256, s, k1.get(), i1.get(), nnz, nbuckets,
-                                    d_rp.get(), n, d_col_src, d_val_src, d_srow, d_off.get(), d_poff.get(), p.d_s_col,
-                                    p.d_s_row, p.d_s_val));
+                                    d_rp.get(), n, d_col_src, d_val_src, d_srow, d_off.get(), d_poff.get(), p.sweep.col.get(),
+                                    p.sweep.row.get(), p.sweep.val.get()));
     }
-    SPMV_BUILD_TRY(launch_items(k_sweep_pad<ValueType>, S, 256, s, S, d_srow, d_off.get(), d_poff.get(), p.d_s_col,
-                                p.d_s_row, p.d_s_val));
+    SPMV_BUILD_TRY(launch_items(k_sweep_pad<ValueType>, S, 256, s, S, d_srow, d_off.get(), d_poff.get(), p.sweep.col.get(),
+                                p.sweep.row.get(), p.sweep.val.get()));
     SPMV_BUILD_TRY(hipStreamSynchronize(s));  // the scratch goes with the scope
     return 0;
 }
 
-// Build step 2: the base column of every 128-entry chunk (p.d_s_cbase), which chunks span
+// Build step 2: the base column of every 128-entry chunk (p.sweep.cbase.get()), which chunks span
 // >= 65536 columns (d_wide: side-table chunks) and how many do (*bad).
 static int sweep_chunk_bases(spmv_plan &p, hipStream_t s, device_buf<uint8_t> &d_wide, uint32_t *bad)
 {
-    const uint64_t nchunks = p.ent_pad / kSweepChunk;
+    const uint64_t nchunks = p.panels.ent_pad / kSweepChunk;
     device_buf<uint32_t> d_bad;
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_cbase, std::max<uint64_t>(nchunks, 1) * 4));
+    SPMV_BUILD_TRY(p.sweep.cbase.alloc(std::max<uint64_t>(nchunks, 1)));
     SPMV_BUILD_TRY(d_bad.alloc(1));
     SPMV_BUILD_TRY(hipMemsetAsync(d_bad, 0, 4, s));
     SPMV_BUILD_TRY(d_wide.alloc(std::max<uint64_t>(nchunks, 1)));
     if (nchunks)
-        SPMV_BUILD_TRY(launch_items(k_sweep_chunk_base, nchunks, 256, s, p.d_s_col, nchunks, (uint32_t)kSweepChunk,
-                                    p.d_s_cbase, d_bad.get(), d_wide.get()));
+        SPMV_BUILD_TRY(launch_items(k_sweep_chunk_base, nchunks, 256, s, p.sweep.col.get(), nchunks, (uint32_t)kSweepChunk,
+                                    p.sweep.cbase.get(), d_bad.get(), d_wide.get()));
     *bad = 0;
     SPMV_BUILD_TRY(hipMemcpyAsync(bad, d_bad, 4, hipMemcpyDeviceToHost, s));
     SPMV_BUILD_TRY(hipStreamSynchronize(s));
@@ -1485,30 +1488,29 @@ static int sweep_pack(spmv_plan &p, hipStream_t s, bool wide, bool lane, const d
                       device_buf<uint32_t> &d_abs)
 {
     if (wide) {
-        SPMV_BUILD_TRY(d_abs.alloc(p.ent_pad));
-        SPMV_BUILD_TRY(launch_items(k_sweep_lane_order_u32, p.ent_pad, 256, s, p.d_s_col, p.ent_pad, d_abs.get()));
-        p.sweep_wide = true;
+        SPMV_BUILD_TRY(d_abs.alloc(p.panels.ent_pad));
+        SPMV_BUILD_TRY(launch_items(k_sweep_lane_order_u32, p.panels.ent_pad, 256, s, p.sweep.col.get(), p.panels.ent_pad, d_abs.get()));
+        p.sweep.wide = true;
     }
-    SPMV_BUILD_TRY(launch_items(k_sweep_pack_rc, p.ent_pad, 256, s, p.d_s_col, p.d_s_row, p.d_s_cbase, p.ent_pad, 7u,
+    SPMV_BUILD_TRY(launch_items(k_sweep_pack_rc, p.panels.ent_pad, 256, s, p.sweep.col.get(), p.sweep.row.get(), p.sweep.cbase.get(), p.panels.ent_pad, 7u,
                                 d_wide.get()));
     SPMV_BUILD_TRY(hipStreamSynchronize(s));
-    SPMV_BUILD_TRY(hipFree(p.d_s_row));
-    p.d_s_row = nullptr;
-    p.sweep_packed = true;
+    SPMV_BUILD_TRY(p.sweep.row.release());
+    p.sweep.packed = true;
     if (!lane)
         return 0;
     device_buf<uint32_t> rc2;
     device_buf<ValueType> v2;
-    SPMV_BUILD_TRY(rc2.alloc(p.ent_pad));
-    SPMV_BUILD_TRY(v2.alloc(p.ent_pad));
-    SPMV_BUILD_TRY(launch_items(k_sweep_lane_order<ValueType>, p.ent_pad, 256, s, p.d_s_col, p.d_s_val, p.ent_pad,
+    SPMV_BUILD_TRY(rc2.alloc(p.panels.ent_pad));
+    SPMV_BUILD_TRY(v2.alloc(p.panels.ent_pad));
+    SPMV_BUILD_TRY(launch_items(k_sweep_lane_order<ValueType>, p.panels.ent_pad, 256, s, p.sweep.col.get(), p.sweep.val.get(), p.panels.ent_pad,
                                 rc2.get(), v2.get()));
     SPMV_BUILD_TRY(hipStreamSynchronize(s));
-    rc2.swap(p.d_s_col);  // the plan takes the lane-ordered arrays; the CSR-ordered ones are
-    v2.swap(p.d_s_val);   // freed here, before the delta form allocates
+    rc2.swap(p.sweep.col);  // the plan takes the lane-ordered arrays; the CSR-ordered ones are
+    v2.swap(p.sweep.val);   // freed here, before the delta form allocates
     SPMV_BUILD_TRY(rc2.release());
     SPMV_BUILD_TRY(v2.release());
-    p.sweep_lane_order = true;
+    p.sweep.lane_order = true;
     return 0;
 }
 
@@ -1517,16 +1519,16 @@ static int sweep_pack(spmv_plan &p, hipStream_t s, bool wide, bool lane, const d
 static int sweep_delta_encode(spmv_plan &p, hipStream_t s, const device_buf<uint8_t> &d_wide,
                               const device_buf<uint32_t> &d_abs)
 {
-    const uint64_t nchunks = p.ent_pad / kSweepChunk;
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_row16, p.ent_pad * 2));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_d8, p.ent_pad));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_dbase, nchunks * 4));
+    const uint64_t nchunks = p.panels.ent_pad / kSweepChunk;
+    SPMV_BUILD_TRY(p.sweep.row16.alloc(p.panels.ent_pad));
+    SPMV_BUILD_TRY(p.sweep.d8.alloc(p.panels.ent_pad));
+    SPMV_BUILD_TRY(p.sweep.dbase.alloc(nchunks));
     std::vector<uint8_t> hf(nchunks);
     {
         device_buf<uint8_t> d_flag;
         SPMV_BUILD_TRY(d_flag.alloc(nchunks));
-        SPMV_BUILD_TRY(launch_items(k_sweep_delta<ValueType>, nchunks, 64, s, p.d_s_col, p.d_s_val, nchunks, p.d_s_row16,
-                                    p.d_s_d8, d_flag.get(), d_wide.get()));
+        SPMV_BUILD_TRY(launch_items(k_sweep_delta<ValueType>, nchunks, 64, s, p.sweep.col.get(), p.sweep.val.get(), nchunks, p.sweep.row16.get(),
+                                    p.sweep.d8.get(), d_flag.get(), d_wide.get()));
         SPMV_BUILD_TRY(hipMemcpyAsync(hf.data(), d_flag, nchunks, hipMemcpyDeviceToHost, s));
         SPMV_BUILD_TRY(hipStreamSynchronize(s));
     }
@@ -1535,23 +1537,22 @@ static int sweep_delta_encode(spmv_plan &p, hipStream_t s, const device_buf<uint
     for (uint64_t c = 0; c < nchunks; ++c)
         if (hf[c])
             sidx[c] = (uint32_t)ns++;
-    p.sweep_side_chunks = ns;
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_side, std::max<uint64_t>(ns, 1) * kSweepChunk * 4));
+    p.sweep.side_chunks = ns;
+    SPMV_BUILD_TRY(p.sweep.side.alloc(std::max<uint64_t>(ns, 1) * kSweepChunk));
     device_buf<uint32_t> d_sidx;
     SPMV_BUILD_TRY(d_sidx.alloc(nchunks));
     SPMV_BUILD_TRY(hipMemcpyAsync(d_sidx, sidx.data(), nchunks * 4, hipMemcpyHostToDevice, s));
-    SPMV_BUILD_TRY(launch_items(k_sweep_delta_base, nchunks, 256, s, p.d_s_col, p.d_s_cbase, d_sidx.get(), nchunks,
-                                p.d_s_dbase, p.d_s_side, d_wide.get(), d_abs.get()));
+    SPMV_BUILD_TRY(launch_items(k_sweep_delta_base, nchunks, 256, s, p.sweep.col.get(), p.sweep.cbase.get(), d_sidx.get(), nchunks,
+                                p.sweep.dbase.get(), p.sweep.side.get(), d_wide.get(), d_abs.get()));
     SPMV_BUILD_TRY(hipStreamSynchronize(s));
     SPMV_BUILD_TRY(d_sidx.release());
-    p.sweep_delta = true;
+    p.sweep.delta = true;
     // split plans can run the measurement build's work-stealing variants (the separate
     // combine kernel re-arms the counters)
-    p.sweep_steal = p.sweep_split > 1 && p.d_steal && !p.d_panel_cnt;
+    p.sweep.can_steal = p.sweep.split > 1 && p.sweep.steal.get() && !p.sweep.panel_cnt.get();
     // the default kernel reads only the 11-byte entries: the rc words are freed
     // (rebuilt by sweep_materialize_rc for a variant that reads them)
-    SPMV_BUILD_TRY(hipFree(p.d_s_col));
-    p.d_s_col = nullptr;
+    SPMV_BUILD_TRY(p.sweep.col.release());
     return 0;
 }
 
@@ -1563,13 +1564,13 @@ int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src,
     const IndexType n = p.nr_rows;
     // spmv_multi's one-pass sweep (sweep_multi.hip): K accumulators per row, so K-fold smaller panels;
     // one workgroup per panel (never split: no partial sums, no combine) and the unpacked entries
-    const bool multi = p.sweep_nvec > 1;
+    const bool multi = p.sweep.nvec > 1;
     // accumulator: fp64, or fp32 (compare-and-swap adds) for fp32 matrices with env SPMV_SWEEP_ACC=32
     const char *aenv = ablation_env("SPMV_SWEEP_ACC");
-    p.sweep_acc_bytes = sizeof(ValueType) == 4 && aenv && std::atoi(aenv) == 32 && !multi ? 4 : 8;
-    const uint64_t acc = p.sweep_acc_bytes;
+    p.sweep.acc_bytes = sizeof(ValueType) == 4 && aenv && std::atoi(aenv) == 32 && !multi ? 4 : 8;
+    const uint64_t acc = p.sweep.acc_bytes;
     // a workgroup of T threads gets T/1024 of one CU's LDS for its panel's y
-    const uint32_t rmax = sweep_rmax(p.sweep_threads, acc, p.sweep_nvec);
+    const uint32_t rmax = sweep_rmax(p.sweep_threads, acc, p.sweep.nvec);
     const int chip_cus = device_cu_count(p.device);
     panel_options po;
     po.wgs = (uint64_t)chip_cus * (1024 / p.sweep_threads);  // resident workgroups per round
@@ -1608,19 +1609,19 @@ int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src,
                                   xbias_split, u, multi))  // (multi: one unit per panel, always)
         return rc;
     const uint32_t P = (uint32_t)(cut.prow.size() - 1), U = u.punit[P];
-    p.npanels = P;
-    p.panel_rmax = u.rmax_used;
-    p.ent_pad = u.poff[P];
-    p.sweep_det = det && !multi;
-    p.xbias_split = u.xbias_split;
-    p.sweep_split = u.sweep_split;  // > 1: combine kernel needed
-    p.nunits = U;
+    p.panels.npanels = P;
+    p.panels.rmax = u.rmax_used;
+    p.panels.ent_pad = u.poff[P];
+    p.sweep.det = det && !multi;
+    p.sweep.xbias_split = u.xbias_split;
+    p.sweep.split = u.sweep_split;  // > 1: combine kernel needed
+    p.sweep.nunits = U;
     if (u.sweep_split > 1) {
-        SPMV_BUILD_TRY(hipMalloc((void **)&p.d_part, (uint64_t)U * (uint64_t(u.rmax_used) + 1) * acc));
+        SPMV_BUILD_TRY(p.sweep.part.alloc_bytes((uint64_t)U * (uint64_t(u.rmax_used) + 1) * acc));
 #ifdef SPMV_ABLATIONS
         // work-stealing counters of the measurement variants (zero; every k_sweep_combine re-arms them)
-        SPMV_BUILD_TRY(hipMalloc((void **)&p.d_steal, (uint64_t)U * 8));
-        SPMV_BUILD_TRY(hipMemsetAsync(p.d_steal, 0, (uint64_t)U * 8, s));
+        SPMV_BUILD_TRY(p.sweep.steal.alloc(U));
+        SPMV_BUILD_TRY(hipMemsetAsync(p.sweep.steal.get(), 0, (uint64_t)U * 8, s));
 #endif
         // env SPMV_SWEEP_COMBINE=fused: the last piece of each panel combines inside the sweep
         // launch instead of k_sweep_combine. Measured slower (0.147 vs 0.128 ms on the N = 8 slice of
@@ -1628,22 +1629,22 @@ int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src,
         // partials alone where the combine kernel reads them with the whole chip
         const char *cenv = ablation_env("SPMV_SWEEP_COMBINE");
         if (cenv && std::strcmp(cenv, "fused") == 0) {
-            SPMV_BUILD_TRY(hipMalloc((void **)&p.d_panel_cnt, std::max<uint64_t>(P, 1) * 4));
-            SPMV_BUILD_TRY(hipMemsetAsync(p.d_panel_cnt, 0, std::max<uint64_t>(P, 1) * 4, s));
+            SPMV_BUILD_TRY(p.sweep.panel_cnt.alloc(std::max<uint64_t>(P, 1)));
+            SPMV_BUILD_TRY(hipMemsetAsync(p.sweep.panel_cnt.get(), 0, std::max<uint64_t>(P, 1) * 4, s));
         }
     }
-    const uint64_t ents = std::max<uint64_t>(p.ent_pad, 4);
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_unit_panel, u.upanel.size() * 4));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_panel_unit, u.punit.size() * 4));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_panel_row, (P + 1) * 4));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_unit_ent, u.uent.size() * 4));
-    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_unit_panel, u.upanel.data(), u.upanel.size() * 4, hipMemcpyHostToDevice, s));
-    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_panel_unit, u.punit.data(), u.punit.size() * 4, hipMemcpyHostToDevice, s));
-    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_panel_row, cut.prow.data(), (P + 1) * 4, hipMemcpyHostToDevice, s));
-    SPMV_BUILD_TRY(hipMemcpyAsync(p.d_unit_ent, u.uent.data(), u.uent.size() * 4, hipMemcpyHostToDevice, s));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_col, ents * 4));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_row, ents * 2));
-    SPMV_BUILD_TRY(hipMalloc((void **)&p.d_s_val, ents * sizeof(ValueType)));
+    const uint64_t ents = std::max<uint64_t>(p.panels.ent_pad, 4);
+    SPMV_BUILD_TRY(p.sweep.unit_panel.alloc(u.upanel.size()));
+    SPMV_BUILD_TRY(p.sweep.panel_unit.alloc(u.punit.size()));
+    SPMV_BUILD_TRY(p.panels.row.alloc(P + 1));
+    SPMV_BUILD_TRY(p.sweep.unit_ent.alloc(u.uent.size()));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.sweep.unit_panel.get(), u.upanel.data(), u.upanel.size() * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.sweep.panel_unit.get(), u.punit.data(), u.punit.size() * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.panels.row.get(), cut.prow.data(), (P + 1) * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(hipMemcpyAsync(p.sweep.unit_ent.get(), u.uent.data(), u.uent.size() * 4, hipMemcpyHostToDevice, s));
+    SPMV_BUILD_TRY(p.sweep.col.alloc(ents));
+    SPMV_BUILD_TRY(p.sweep.row.alloc(ents));
+    SPMV_BUILD_TRY(p.sweep.val.alloc(ents));
 
     if (int rc = sweep_sort_entries(p, u, h_rp, d_col_src, d_val_src, s))
         return rc;
@@ -1654,7 +1655,7 @@ int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src,
     uint32_t bad = 0;
     if (int rc = sweep_chunk_bases(p, s, d_wide, &bad))
         return rc;
-    const uint64_t nchunks = p.ent_pad / kSweepChunk;
+    const uint64_t nchunks = p.panels.ent_pad / kSweepChunk;
     const char *env = ablation_env("SPMV_SWEEP_PACKED");
     const bool want = !(env && env[0] == '0');
     const char *lo = ablation_env("SPMV_SWEEP_LANE_ORDER");
@@ -1673,15 +1674,14 @@ int build_sweep(spmv_plan &p, const IndexType *h_rp, const IndexType *d_col_src,
     // 11-byte entries). Side chunks stream 15 B per entry, so when more than 1 chunk in 10 is
     // wide (sparse panels throughout), or without the delta form, the plan keeps the
     // unpacked 14-byte entries
-    if ((!bad || (delta && uint64_t(bad) * 10 <= nchunks)) && want && p.ent_pad) {
+    if ((!bad || (delta && uint64_t(bad) * 10 <= nchunks)) && want && p.panels.ent_pad) {
         if (int rc = sweep_pack(p, s, bad != 0, lane, d_wide, d_abs))
             return rc;
         if (delta)
             if (int rc = sweep_delta_encode(p, s, d_wide, d_abs))
                 return rc;
     } else {
-        SPMV_BUILD_TRY(hipFree(p.d_s_cbase));
-        p.d_s_cbase = nullptr;
+        SPMV_BUILD_TRY(p.sweep.cbase.release());
     }
     SPMV_BUILD_TRY(hipStreamSynchronize(s));
     return 0;
@@ -1693,17 +1693,18 @@ int probe_locality(const IndexType *d_rp, const IndexType *d_col, IndexType n, h
     *frac = 1.0;
     if (n == 0)
         return 0;
-    unsigned long long *d_cnt = nullptr, h[2] = {0, 0};
-    SPMV_TRY(hipMalloc((void **)&d_cnt, 16));
+    device_buf<unsigned long long> d_cnt;
+    unsigned long long h[2] = {0, 0};
+    SPMV_TRY(d_cnt.alloc(2));
     SPMV_TRY(hipMemsetAsync(d_cnt, 0, 16, s));
     const uint32_t stride = std::max<uint32_t>(1, n / 65536);
     const uint64_t threads = (n + stride - 1) / stride;
     hipLaunchKernelGGL(k_locality, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_rp, d_col, n, stride,
-                       d_cnt);
+                       d_cnt.get());
     SPMV_TRY(hipGetLastError());
     SPMV_TRY(hipMemcpyAsync(h, d_cnt, 16, hipMemcpyDeviceToHost, s));
     SPMV_TRY(hipStreamSynchronize(s));
-    SPMV_TRY(hipFree(d_cnt));
+    SPMV_TRY(d_cnt.release());
     *frac = h[0] ? double(h[1]) / double(h[0]) : 1.0;
     return 0;
 }
@@ -1716,27 +1717,27 @@ static hipError_t sweep_launch(const spmv_plan &p, const ValueType *d_x, ValueTy
 
 static void sweep_warm(const spmv_plan &p, hipStream_t s)
 {
-    if (p.sweep_nvec > 1)  // spmv_multi's plan: run only by launch_sweep_multi
-        (void)launch_sweep_multi(p, p.sweep_nvec, nullptr, nullptr, s, true);
+    if (p.sweep.nvec > 1)  // spmv_multi's plan: run only by launch_sweep_multi
+        (void)launch_sweep_multi(p, p.sweep.nvec, nullptr, nullptr, s, true);
     else
         (void)launch_sweep(p, nullptr, nullptr, s, true);
 }
 
 static uint64_t sweep_device_bytes(const spmv_plan &p)
 {
-    return p.ent_pad * ((p.d_s_col ? sizeof(uint32_t) : 0) + (p.sweep_packed ? 0 : sizeof(uint16_t)) + sizeof(ValueType)) +
-           (p.npanels + 1) * 4 + (p.nunits + 1) * 4 + (p.sweep_packed ? p.ent_pad / kSweepChunk * 4 : 0) +
-           (p.sweep_split > 1 ? p.nunits * (uint64_t(p.panel_rmax) + 1) * p.sweep_acc_bytes : 0) + p.nunits * 4 + (p.npanels + 1) * 4 +
-           (p.d_panel_cnt ? p.npanels * 4 : 0) +
-           (p.sweep_delta ? p.ent_pad * 3 + p.ent_pad / kSweepChunk * 4 + p.sweep_side_chunks * kSweepChunk * 4 : 0);
+    return p.panels.ent_pad * ((p.sweep.col.get() ? sizeof(uint32_t) : 0) + (p.sweep.packed ? 0 : sizeof(uint16_t)) + sizeof(ValueType)) +
+           (p.panels.npanels + 1) * 4 + (p.sweep.nunits + 1) * 4 + (p.sweep.packed ? p.panels.ent_pad / kSweepChunk * 4 : 0) +
+           (p.sweep.split > 1 ? p.sweep.nunits * (uint64_t(p.panels.rmax) + 1) * p.sweep.acc_bytes : 0) + p.sweep.nunits * 4 + (p.panels.npanels + 1) * 4 +
+           (p.sweep.panel_cnt.get() ? p.panels.npanels * 4 : 0) +
+           (p.sweep.delta ? p.panels.ent_pad * 3 + p.panels.ent_pad / kSweepChunk * 4 + p.sweep.side_chunks * kSweepChunk * 4 : 0);
 }
 
 static int sweep_format_bits(const spmv_plan &p)
 {
-    const bool stealing = p.sweep_steal && p.sweep_variant >= 37 && p.sweep_variant <= 39;
-    return (p.sweep_packed ? 2 : 0) | (p.sweep_lane_order ? 4 : 0) | (p.sweep_delta ? 64 : 0) | (stealing ? 128 : 0) |
-           (p.sweep_split > 1 && p.xbias_split > 0.0 ? 1024 : 0) | (p.sweep_split > 1 && p.xbias_split < 0.0 ? 2048 : 0) |
-           (p.sweep_wide ? 4096 : 0) | (p.sweep_nvec > 1 ? 8192 : 0);
+    const bool stealing = p.sweep.can_steal && p.sweep.variant >= 37 && p.sweep.variant <= 39;
+    return (p.sweep.packed ? 2 : 0) | (p.sweep.lane_order ? 4 : 0) | (p.sweep.delta ? 64 : 0) | (stealing ? 128 : 0) |
+           (p.sweep.split > 1 && p.sweep.xbias_split > 0.0 ? 1024 : 0) | (p.sweep.split > 1 && p.sweep.xbias_split < 0.0 ? 2048 : 0) |
+           (p.sweep.wide ? 4096 : 0) | (p.sweep.nvec > 1 ? 8192 : 0);
 }
 
 static int sweep_set_variant(spmv_plan &p, int variant)
@@ -1749,7 +1750,7 @@ static int sweep_set_variant(spmv_plan &p, int variant)
     // variants 37-39 reads the 12-byte rc words, which a delta plan rebuilds on first use
     if ((variant < 36 || variant > 39) && variant != 28 && sweep_materialize_rc(p))
         return 1;
-    p.sweep_variant = variant;
+    p.sweep.variant = variant;
     return 0;
 }
 
@@ -1759,13 +1760,13 @@ const layout_ops &sweep_layout()
         "sweep", "build sweep layout", build_sweep, kKernelTiles,  // (32-bit entry offsets overflow: the tiles have none)
         nullptr, sweep_launch, nullptr, sweep_warm,
         sweep_device_bytes,
-        [](const spmv_plan &p) -> uint64_t { return p.nunits; },                             // units: panel pieces
-        [](const spmv_plan &p) -> uint64_t { return p.nunits ? p.ent_pad / p.nunits : 0; },  // unit_nnz
+        [](const spmv_plan &p) -> uint64_t { return p.sweep.nunits; },                             // units: panel pieces
+        [](const spmv_plan &p) -> uint64_t { return p.sweep.nunits ? p.panels.ent_pad / p.sweep.nunits : 0; },  // unit_nnz
         one_block,
         sweep_format_bits,
-        [](const spmv_plan &p) -> uint64_t { return p.ent_pad; },                                           // stored_entries
-        [](const spmv_plan &p) -> void * { return p.d_s_col ? (void *)p.d_s_col : (void *)p.d_s_row16; },  // index_stream
-        1, {28, kSweepTurnOrdered}, sweep_set_variant, true,  // tune_slot, product_variants, set_variant, host_y
+        [](const spmv_plan &p) -> uint64_t { return p.panels.ent_pad; },                                           // stored_entries
+        [](const spmv_plan &p) -> void * { return p.sweep.col ? p.sweep.col.p : p.sweep.row16.p; },  // index_stream
+        1, {28, kSweepTurnOrdered}, sweep_set_variant, true, sweep_flags_panels,  // tune_slot, product_variants, set_variant, host_y, flags_panels
     };
     return row;
 }

@@ -2,7 +2,7 @@
 //
 // Y = A X for K = 2, 4 or 8 right-hand sides in one pass over a scattered matrix, X and Y
 // row-major (X[c * K + j]). The layout is the sweep build's unpacked one, sized for K
-// accumulators per row (build_sweep with spmv_plan::sweep_nvec = K, never split): s_col u32,
+// accumulators per row (build_sweep with spmv_plan::sweep.nvec = K, never split): s_col u32,
 // s_row u16, s_val V per entry, panels contiguous and padded to whole 128-entry chunks, ascending
 // column per panel; panel_row u32[P + 1]; unit_ent u32[P + 1] (one unit per panel, so it holds
 // every panel's first padded entry). One workgroup owns one panel: its R x K sums live in LDS as
@@ -147,10 +147,12 @@ constexpr int sweep_multi_groups()
 template <int K, int T>
 static void launch_sweep_multi_t(const spmv_plan &p, const ValueType *d_X, ValueType *d_Y, hipStream_t s, bool warm)
 {
-    const size_t lds = (size_t(p.panel_rmax) + 1) * K * sizeof(double);
+    const sweep_state &w = p.sweep;
+    const size_t lds = (size_t(p.panels.rmax) + 1) * K * sizeof(double);
     launch_or_warm(warm, k_spmv_sweep_multi<ValueType, K, T, sweep_multi_groups<ValueType, K>(), SPMV_MULTI_SWEEP_VMAJOR != 0>,
-                   dim3((unsigned)p.npanels), dim3(T), lds, s, (const uint32_t *)p.d_s_col, (const uint16_t *)p.d_s_row,
-                   (const ValueType *)p.d_s_val, (const uint32_t *)p.d_panel_row, (const uint32_t *)p.d_unit_ent, d_X, d_Y);
+                   dim3((unsigned)p.panels.npanels), dim3(T), lds, s, (const uint32_t *)w.col.get(), (const uint16_t *)w.row.get(),
+                   (const ValueType *)w.val.get(), (const uint32_t *)p.panels.row.get(), (const uint32_t *)w.unit_ent.get(), d_X,
+                   d_Y);
 }
 
 template <int K>
@@ -164,14 +166,14 @@ static void launch_sweep_multi_k(const spmv_plan &p, const ValueType *d_X, Value
 }
 
 // d_Y[nr_rows x nvec] = A * d_X[nr_cols x nvec], both row-major, on a sweep plan built with
-// sweep_nvec = nvec (2, 4 or 8): unpacked entries, one unit per panel, no partial sums
+// sweep.nvec = nvec (2, 4 or 8): unpacked entries, one unit per panel, no partial sums
 hipError_t launch_sweep_multi(const spmv_plan &p, int nvec, const ValueType *d_X, ValueType *d_Y, hipStream_t s,
                               bool warm)
 {
-    if (p.kernel != kKernelSweep || p.sweep_nvec != nvec || (nvec != 2 && nvec != 4 && nvec != 8) || p.sweep_packed ||
-        p.sweep_split != 1 || p.nunits != p.npanels || p.sweep_acc_bytes != 8)
+    if (p.kernel != kKernelSweep || p.sweep.nvec != nvec || (nvec != 2 && nvec != 4 && nvec != 8) || p.sweep.packed ||
+        p.sweep.split != 1 || p.sweep.nunits != p.panels.npanels || p.sweep.acc_bytes != 8)
         return hipErrorInvalidValue;
-    if (p.npanels == 0)
+    if (p.panels.npanels == 0)
         return hipSuccess;
     if (nvec == 2)
         launch_sweep_multi_k<2>(p, d_X, d_Y, s, warm);

@@ -225,3 +225,58 @@ def test_binned_pass1_cache_policy_variants(monkeypatch, dtype, variant):
     err = oracle.scaled_error(r, c, h[2], h[3], ref, y.cpu().numpy())
     assert err <= (1e-12 if dtype == np.float64 else 2e-6), err
     plan.destroy()
+
+
+# ---- buffers a plan allocates after its build, and frees with the plan ----
+
+def _check(plan, x, n, h, ref, dtype):
+    import torch
+    import oracle
+    y = torch.full((n,), float("nan"), dtype=x.dtype, device="cuda")
+    plan.run(x, y)
+    torch.cuda.synchronize()
+    err = oracle.scaled_error(h[0].view(np.uint32), h[1].view(np.uint32), h[2], h[3], ref, y.cpu().numpy())
+    assert err <= (1e-12 if dtype == np.float64 else 2e-6), err
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_sweep_rc_words_rebuilt_then_freed_with_the_plan(monkeypatch, dtype):
+    """A delta plan keeps only the 11-byte entries; variant 94 rebuilds the 12-byte rc words
+    (sweep_materialize_rc). y matches the oracle on the rebuilt words and back on the default
+    kernel; the plan is destroyed while it holds them, and a second plan of the same matrix then
+    runs the same sequence."""
+    import oracle
+    n, z = 50_000, 800_000
+    for _ in range(2):
+        lib, plan, x = _plan(monkeypatch, "sweep", dtype, n, z)
+        st = plan.stats()
+        assert st["kernel"] == 2 and st["format"] & 64  # delta-coded columns: no rc words yet
+        rp, col, val, _ = spmv_hw.gen_powerlaw(lib, n, n, z, seed=4)
+        h = [t.cpu().numpy() for t in (rp, col, val, x)]
+        ref = oracle.spmv_gold(h[0].view(np.uint32), h[1].view(np.uint32), h[2], h[3])
+        _check(plan, x, n, h, ref, dtype)
+        plan.set_variant(94)
+        assert plan.stats()["device_bytes"] > st["device_bytes"]  # the rc words are resident
+        _check(plan, x, n, h, ref, dtype)
+        plan.set_variant(0)
+        _check(plan, x, n, h, ref, dtype)
+        plan.destroy()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_binned_rebased_offsets_replaced_then_freed_with_the_plan(monkeypatch, dtype):
+    """Binned variants 1 and 2 each allocate the rebased segment offsets: setting 2 after 1
+    replaces them, and the plan is destroyed while it holds them. y matches the oracle under
+    both, and on a second plan of the same matrix afterwards."""
+    import oracle
+    n, z = 200_000, 3_200_000
+    for _ in range(2):
+        lib, plan, x = _plan(monkeypatch, "binned", dtype, n, z)
+        assert plan.stats()["kernel"] == 6
+        rp, col, val, _ = spmv_hw.gen_powerlaw(lib, n, n, z, seed=4)
+        h = [t.cpu().numpy() for t in (rp, col, val, x)]
+        ref = oracle.spmv_gold(h[0].view(np.uint32), h[1].view(np.uint32), h[2], h[3])
+        for variant in (1, 2):
+            plan.set_variant(variant)
+            _check(plan, x, n, h, ref, dtype)
+        plan.destroy()
